@@ -1,6 +1,6 @@
 """bench.py — edges/sec per tumbling slice for reduceOnEdges on the BASELINE C2 window.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): one tumbling window of an R-MAT scale-24
 stream (Graph500 a,b,c,d = .57,.19,.19,.05, edge factor 16 -> E = 2^28 edges, seeded vertex
@@ -9,7 +9,11 @@ A step = the whole window through the engine with the edge columns already resid
 key scan -> LSD radix passes -> segmented reduce -> per-vertex (vertex, sum) in HBM.
 N > 1 (torchrun, one rank per GPU): each rank holds its own 2^28-edge slice of the stream
 (weak scaling); the step adds the RCCL keyBy exchange of per-vertex partials and the merge.
-Rank 0 prints one JSON line (roofline of the dominant kernel + the CPU baseline at N = 1).
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the line (with
+the roofline of the dominant kernel, whose events the timed windows record); --dump-outputs DIR also
+writes what the last timed step returned.  --full adds what takes runs of its own: the CPU baseline at
+N = 1, the stage-timed windows behind the whole per-kernel table, and the secondary workloads' checks
+of their results against the oracle.
 """
 from __future__ import annotations
 
@@ -41,7 +45,14 @@ def parse():
     p.add_argument("--edge-factor", type=int, default=16)
     p.add_argument("--seed", type=lambda x: int(x, 0), default=0x5EED02)
     p.add_argument("--dtype", default="int64", choices=["int64", "float64"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the CPU baseline "
+                        "(unless --no-cpu-baseline), the stage-timed windows behind the per-kernel table, and the "
+                        "workloads' own result checks against the oracle")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float64; "
+                        "at most 64 MB in all: a fixed seeded sample of the rows of a larger output)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--alloc-outputs", action="store_true",
                    help="reduce / fold: allocate the output tensors per window (A/B; default: reused across windows, as a streaming operator keeps its buffers)")
     p.add_argument("--cpu-sample-log2", type=int, default=30,
@@ -109,7 +120,37 @@ def parse():
                    help="reduce = C2 (default, the headline); fold = C3 degree/max on skewed R-MAT; "
                         "triangles = WindowTriangles on an R-MAT window without self-loops (C4 shape); "
                         "cc = ConnectedComponents of an R-MAT window (SURVEY.md §8f#4)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:   # a plain run times its steps and prints the line: no CPU leg
+        a.no_cpu_baseline = True
+    return a
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all files of one run together stay below this
+
+
+def dump_outputs(directory, *groups):
+    """--dump-outputs: each group maps the names of row-aligned columns to what the last timed step returned
+    under them (tensors, arrays or scalars); every column becomes DIR/<name>.npy.  Everything is written as
+    float64 (exact for the integers this library produces: ids, counts and sums stay below 2^53).  A group
+    whose share of the 64 MB does not hold all of its rows is sampled: the same sorted, seeded row indices
+    for each of its columns, and the same from run to run."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    groups = [{n: c for n, c in g.items() if c is not None} for g in groups]
+    ncols = max(1, sum(len(g) for g in groups))
+    budget_rows = (DUMP_BYTES - 4096 * ncols) // (8 * ncols)   # rows per column (.npy headers aside)
+    for g in groups:
+        idx = None
+        for name, c in g.items():
+            c = c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))
+            c = c.reshape(-1)
+            if idx is None and c.numel() > budget_rows:
+                gen = torch.Generator().manual_seed(0x5EED0D)
+                idx = torch.randperm(c.numel(), generator=gen)[:budget_rows].sort().values
+            if idx is not None:
+                c = c.index_select(0, idx.to(c.device))
+            np.save(d / f"{name}.npy", c.to(torch.float64).cpu().numpy())
 
 
 def algorithmic_bytes(workload, E, U, vb=8):
@@ -430,19 +471,28 @@ def window_stream_main(a):
         a_, b_, f_ = r
         P = int(a_.numel())
         extra.update(candidate_records=P, candidates_per_s=P * a.steps / elapsed)
-        # stage 2 (keyBy(0,1) CountTriangles + sum(0)) on the emitted records, checked against the
+        # --full: stage 2 (keyBy(0,1) CountTriangles + sum(0)) on the emitted records, checked against the
         # direct triangle count of the same window
-        t2 = []
-        for _ in range(3):
-            tt = time.perf_counter()
-            c2 = eng.count_candidates(a_, b_, f_)
-            torch.cuda.synchronize()
-            t2.append(time.perf_counter() - tt)
-        tri = eng.triangles(*wins[(a.steps - 1) % len(wins)])
-        assert c2[0] == tri[0], "stage-2 count differs from the window's triangle count"
-        extra.update(stage2_ms=statistics.median(t2) * 1e3, stage2_records_per_s=P / statistics.median(t2),
-                     triangles=c2[0], stage2_emitting_groups=c2[3])
+        if a.full:
+            t2 = []
+            for _ in range(3):
+                tt = time.perf_counter()
+                c2 = eng.count_candidates(a_, b_, f_)
+                torch.cuda.synchronize()
+                t2.append(time.perf_counter() - tt)
+            tri = eng.triangles(*wins[(a.steps - 1) % len(wins)])
+            assert c2[0] == tri[0], "stage-2 count differs from the window's triangle count"
+            extra.update(stage2_ms=statistics.median(t2) * 1e3, stage2_records_per_s=P / statistics.median(t2),
+                         triangles=c2[0], stage2_emitting_groups=c2[3])
         algo = 16 * E + 17 * P
+    if a.dump_outputs:   # what the last timed window returned
+        if a.workload == "c1":
+            dump_outputs(a.dump_outputs, {"triangles": r[0], "reference_integer_output": r[1]})
+        elif a.workload == "apply":
+            dump_outputs(a.dump_outputs, {"vertex": keys}, {"offsets": offs}, {"neighbours": nbrs},
+                         {"candidate_records_needed": P})
+        else:
+            dump_outputs(a.dump_outputs, {"a": a_, "b": b_, "is_candidate": f_})
     ms = statistics.mean(lat) * 1e3
     cpu = None
     if a.workload == "c1" and not a.no_cpu_baseline:
@@ -591,6 +641,10 @@ def cand_stream_main(a):
     wlat_ms = np.array([(ev_ref.elapsed_time(win_end[w]) / 1e3 + t0 - fire[w]) * 1e3 for w in range(len(win_end))])
     s = torch.stack(sums).sum(0).tolist() if sums else [0, 0, 0]
     chk = (s[0] * 31 + s[1] + s[2]) & ((1 << 63) - 1)
+    if a.dump_outputs:   # the records themselves never rest in memory: each window's record count and the
+        # consumer's column sums over all chunks (in halves of 32 bits: the sums pass 2^53)
+        dump_outputs(a.dump_outputs, {"records_per_window": totals},
+                     {"column_sums_hi32": [x >> 32 for x in s], "column_sums_lo32": [x & 0xFFFFFFFF for x in s]})
     cands = total - 2 * E * W   # every record past the 2E edge records (one per slice(ALL) record) is a candidate
     period = elapsed / W
     line = {"metric": "candidate records/s (GenerateCandidateEdges, chunked emission)", "value": total / elapsed,
@@ -686,7 +740,10 @@ def parse_main(a):
         torch.cuda.synchronize()
         lat.append(time.perf_counter() - t)
     elapsed = time.perf_counter() - t0
-    assert torch.equal(r[0], s) and torch.equal(r[1], d), "parsed columns differ from the generated edges"
+    if a.full:
+        assert torch.equal(r[0], s) and torch.equal(r[1], d), "parsed columns differ from the generated edges"
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"src": r[0], "dst": r[1], "ts": r[2]})
     ms = statistics.mean(lat) * 1e3
     algo = len(text) + 24 * n      # text in, three int64 columns out (the staging copy is extra traffic)
     cpu = None
@@ -791,6 +848,9 @@ def e2e_main(a):
         for r in timed[:2]:
             v = host[(r.start // 1000) % ndist][2]
             assert int(r.columns[1].sum()) == int(v.sum()), "e2e window: sum of sums != sum of values"
+    if a.dump_outputs:   # the last timed window's result, as it reached the host
+        last = timed[-1].columns
+        dump_outputs(a.dump_outputs, {"triangles": last[0]} if tri else {"vertex": last[0], "sum": last[1]})
     op.close()
     for p in pinned_bufs:
         L.load().gs_free_pinned(p)
@@ -968,7 +1028,7 @@ def main():
             else:
                 r = D.fold_degree_max_window(fold_partials_timed, M_fold, src, dst, 1, -(1 << 63)) if dist \
                     else local_fold(src, dst, 1, -(1 << 63))
-            return r[0], r[1], local_times[0]
+            return r[0], r[1:], local_times[0]   # (keys, (degree, max neighbour))
         if abi:       # gs_window_reduce_dist
             nonlocal dist_out
             if dist_out is None and not a.alloc_outputs:   # (kept across windows; 2x the slice's records)
@@ -1009,8 +1069,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if a.dump_outputs and rank == 0:   # what the last timed step returned (this rank's rows at N > 1)
+        if a.workload == "triangles":
+            dump_outputs(a.dump_outputs, {"triangles": k})
+        elif a.workload == "fold":   # row-aligned columns: one sample of the rows for all of them
+            dump_outputs(a.dump_outputs, {"vertex": k, "degree": v[0], "max_neighbour": v[1]})
+        else:
+            dump_outputs(a.dump_outputs, {"vertex": k, "label" if a.workload == "cc" else "sum": v})
+
     stage_times_after = None
-    if lean:
+    if lean and a.full:   # (windows of their own: a plain run reports the stages its timed windows recorded)
         eng.set_timing(pkg._lib.GS_TIMING_STAGES)
         stage_times_after = [eng.stage_times_of(step(a.warmup + a.steps + i)[2]) for i in range(3)]
         torch.cuda.synchronize()
@@ -1051,7 +1119,9 @@ def main():
             pmc_window += pmc.get("k_bk_merge_slices", {}).get("bytes_per_launch", 0)
     window_gbs = B / (ms_step * 1e-3) / 1e9 / world
     roofline = {"bound": "hbm", "kernel": dom_name,
-                "achieved": round(B / (dom["ms"] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                # (no stage of this pipeline timed inside the region, and no --full windows after it: no figure)
+                "achieved": round(B / (dom["ms"] * 1e-3) / 1e9, 1) if dom["ms"] > 0 else None,
+                "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(dom["frac_on_B"], 4), "traffic": pmc_dom,
                 "algorithmic_bytes_per_launch": B,
                 "algorithmic_bytes_formula": {"reduce": "16E + 16U (SURVEY.md §8d, reduce OUT, 8-byte values)",
@@ -1069,8 +1139,9 @@ def main():
                                     "same_build": pmc.get("_meta", {}).get("lib_sha16") == lib_sha16()}
                                    if pmc_dom is not None or pmc_window else None),
                 "timing": ("device events on the library's stream (gs_last_stage_times) around the scatter and the "
-                           "accumulate inside the timed region (gs_set_timing DOMINANT); the other stages on 3 "
-                           "windows after it with every stage event") if lean else
+                           "accumulate inside the timed region (gs_set_timing DOMINANT); " +
+                           ("the other stages on 3 windows after it with every stage event" if a.full else
+                            "the other stages are timed only with --full")) if lean else
                           "device events on the library's stream around each launch (gs_last_stage_times)"}
 
     if a.workload == "reduce" and "bucket_accumulate" in kt and dom_name in ("sp_scatter_pack", "sp_scatter",
@@ -1187,7 +1258,8 @@ def main():
             "kernels": {n: {"avg_ms": round(r["ms"], 4), "own_bytes": r["bytes"], "GB/s": round(r["GB/s"], 1),
                             "frac": round(r["frac"], 4),
                             **({"frac_on_B": round(r["frac_on_B"], 4)} if n == dom_name else {})}
-                        for n, r in kt.items()},
+                        for n, r in kt.items() if a.full or not lean or r["ms"] > 0},   # (untimed stages: --full)
+            "full": a.full,
         }
         emit(line)
     if abi:

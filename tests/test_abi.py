@@ -116,15 +116,34 @@ def test_jni_shim_covers_every_native_and_calls_only_declared_entry_points():
 
 def test_dispatch_patch_applies_to_the_reference():
     """java/patches/*.patch (GraphWindowStream's package-private ctor + built-in dispatch, slice() passing
-    the pre-keyBy edges) applies cleanly to the reference tree (checked without writing to it)."""
-    import pytest
-    ref = Path("/root/reference")
-    if not (ref / "src").is_dir():
-        pytest.skip("reference tree not present (GPU box)")
-    for patch in sorted((JAVA / "patches").glob("*.patch")):
-        r = subprocess.run(["git", "apply", "--check", str(patch)], cwd=ref, capture_output=True,
-                           text=True)
-        assert r.returncode == 0, r.stderr
+    the pre-keyBy edges) applies cleanly to the reference tree, decided without the tree: every hunk's
+    pre-image (context + removed lines) must be, line for line, what the reference's file holds at the
+    hunk's position, and the patch must name the reference's own blob of each file.  The digests of the
+    reference's lines are recorded in tests/golden/patch_preimage.json (extract_patch_preimage.py)."""
+    import importlib.util
+    import json
+    golden = Path(__file__).parent / "golden"
+    spec = importlib.util.spec_from_file_location("extract_patch_preimage", golden / "extract_patch_preimage.py")
+    ex = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ex)
+    recorded = json.loads((golden / "patch_preimage.json").read_text())
+    patches = sorted((JAVA / "patches").glob("*.patch"))
+    assert patches and sorted(recorded) == [p.name for p in patches]
+    for patch in patches:
+        text = ex.read_patch(patch)
+        files = ex.hunks_of(text)
+        rec = recorded[patch.name]
+        assert files and sorted(files) == sorted(rec)
+        blobs = dict(re.findall(r"^diff --git a/(\S+) b/\S+\nindex ([0-9a-f]+)\.\.", text, re.M))
+        for name, hunks in files.items():
+            assert rec[name]["blob"].startswith(blobs[name]), (name, "the patch was made against another blob")
+            assert len(hunks) == len(rec[name]["hunks"]), name
+            end = 0
+            for (start, count, pre), want in zip(hunks, rec[name]["hunks"]):
+                assert (start, count) == (want["start"], want["count"]) and len(pre) == count, (name, start)
+                assert start > end, (name, start, "hunks overlap or are out of order")
+                end = start + count - 1
+                assert ex.digest(pre) == want["sha256"], (name, start, "pre-image differs from the reference")
 
 
 GPU_JAVA = JAVA / "src/main/java/org/apache/flink/graph/streaming/gpu"

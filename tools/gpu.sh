@@ -37,7 +37,7 @@ case $MODE in
   bench)
     bench bench "$@" ;;
   c2)
-    bench bench_c2_i64
+    bench bench_c2_i64 --full
     trace trace_c2
     ;&
   c2pmc)
@@ -63,19 +63,19 @@ case $MODE in
       done
     done ;;
   evidence)
-    bench bench_c2_f64 --dtype float64
-    bench bench_c3_rmat --workload fold
-    bench bench_c3_zipf --workload fold --stream zipf
-    bench bench_tri_s20 --workload triangles --scale 20
-    bench bench_tri_s22 --workload triangles --scale 22
-    bench bench_tri_s24 --workload triangles --scale 24
-    bench bench_tri_s26 --workload triangles --scale 26 --steps 3 --warmup 1
-    bench bench_cc_s24 --workload cc
-    bench bench_c1 --workload c1
-    bench bench_apply --workload apply
-    bench bench_candidates --workload candidates
-    bench bench_cand_stream --workload cand_stream
-    bench bench_parse --workload parse
+    bench bench_c2_f64 --full --dtype float64
+    bench bench_c3_rmat --full --workload fold
+    bench bench_c3_zipf --full --workload fold --stream zipf
+    bench bench_tri_s20 --full --workload triangles --scale 20
+    bench bench_tri_s22 --full --workload triangles --scale 22
+    bench bench_tri_s24 --full --workload triangles --scale 24
+    bench bench_tri_s26 --full --workload triangles --scale 26 --steps 3 --warmup 1
+    bench bench_cc_s24 --full --workload cc
+    bench bench_c1 --full --workload c1
+    bench bench_apply --full --workload apply
+    bench bench_candidates --full --workload candidates
+    bench bench_cand_stream --full --workload cand_stream
+    bench bench_parse --full --workload parse
     bench bench_e2e_direct --workload e2e --staging direct --no-cpu-baseline
     bench bench_e2e_pinned --workload e2e --staging pinned --no-cpu-baseline
     bench bench_e2e_buffered --workload e2e --staging buffered --no-cpu-baseline ;;

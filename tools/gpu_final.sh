@@ -22,7 +22,7 @@ case $MODE in
     tail -3 "$O/tests.txt"
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.txt" 2>&1
     cat "$O/smoke.txt" | grep -v amdgpu.ids
-    bash tools/gpu.sh bench "$TAG" ;;
+    bash tools/gpu.sh bench "$TAG" --full ;;
   B)
     bash tools/gpu.sh c2 "$TAG"
     bash tools/gpu.sh tri "$TAG" 24
@@ -46,18 +46,18 @@ case $MODE in
              "bench_e2e_direct --workload e2e --staging direct --no-cpu-baseline" \
              "bench_e2e_pinned --workload e2e --staging pinned --no-cpu-baseline"; do
       set -- $x; n=$1; shift
-      timeout -k 10 300 python3 bench.py "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
+      timeout -k 10 300 python3 bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
     done ;;
   H)   # round 6: triangles (s20 / s22 / s24 lines; s26 with the whole-window 16-thread CPU baseline) and C5
     for x in "bench_tri_s20 --workload triangles --scale 20" "bench_tri_s22 --workload triangles --scale 22" \
              "bench_tri_s24 --workload triangles --scale 24"; do
       set -- $x; n=$1; shift
-      timeout -k 10 300 python3 bench.py "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
+      timeout -k 10 300 python3 bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
     done
-    timeout -k 10 400 python3 bench.py --workload triangles --scale 26 --steps 3 --warmup 1 > "$O/bench_tri_s26.json" 2> "$O/bench_tri_s26.err"
+    timeout -k 10 400 python3 bench.py --full --workload triangles --scale 26 --steps 3 --warmup 1 > "$O/bench_tri_s26.json" 2> "$O/bench_tri_s26.err"
     echo "bench_tri_s26 done"
-    timeout -k 10 300 python3 bench.py --workload cand_stream --cand-windows 4 > "$O/bench_cand_stream.json" 2> "$O/bench_cand_stream.err"
-    timeout -k 10 300 python3 bench.py --workload cand_stream --cand-windows 4 --cand-ids u32 > "$O/bench_cand_stream_u32.json" 2> "$O/bench_cand_stream_u32.err"
+    timeout -k 10 300 python3 bench.py --full --workload cand_stream --cand-windows 4 > "$O/bench_cand_stream.json" 2> "$O/bench_cand_stream.err"
+    timeout -k 10 300 python3 bench.py --full --workload cand_stream --cand-windows 4 --cand-ids u32 > "$O/bench_cand_stream_u32.json" 2> "$O/bench_cand_stream_u32.err"
     timeout -k 10 300 python3 bench.py --workload cand_stream --cand-windows 4 --cand-cadence-ms 1000 --no-cpu-baseline > "$O/bench_cand_stream_cadence.json" 2> "$O/bench_cand_stream_cadence.err" ;;
   I)
     bash tools/gpu.sh c2 "$TAG"
@@ -65,11 +65,11 @@ case $MODE in
     for x in "bench_tri_s20 --workload triangles --scale 20" "bench_tri_s22 --workload triangles --scale 22" \
              "bench_tri_s24 --workload triangles --scale 24"; do
       set -- $x; n=$1; shift
-      timeout -k 10 300 python3 bench.py "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
+      timeout -k 10 300 python3 bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err"; echo "$n done"
     done ;;
   E)
-    timeout -k 10 400 python3 bench.py --workload cand_stream --cand-ids u32 > "$O/bench_cand_stream_u32.json" 2> "$O/bench_cand_stream_u32.err"
-    timeout -k 10 400 python3 bench.py --workload cand_stream > "$O/bench_cand_stream.json" 2> "$O/bench_cand_stream.err"
+    timeout -k 10 400 python3 bench.py --full --workload cand_stream --cand-ids u32 > "$O/bench_cand_stream_u32.json" 2> "$O/bench_cand_stream_u32.err"
+    timeout -k 10 400 python3 bench.py --full --workload cand_stream > "$O/bench_cand_stream.json" 2> "$O/bench_cand_stream.err"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/cand_u32_trace" -o run --output-format csv -- python3 bench.py --workload cand_stream \
       --cand-ids u32 --cand-consumer none --cand-windows 1 --max-chunks 40 --no-cpu-baseline > "$O/cand_u32_trace.log" 2>&1 ;;
 esac
