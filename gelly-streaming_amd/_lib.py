@@ -22,6 +22,7 @@ GS_WATERMARK_EXPLICIT, GS_WATERMARK_ASCENDING = 0, 1
 GS_STAGE_PINNED, GS_STAGE_DIRECT = 0, 1
 GS_MEM_HOST, GS_MEM_DEVICE = 0, 1
 GS_TIMING_OFF, GS_TIMING_DOMINANT, GS_TIMING_STAGES = 0, 1, 2   # gs_set_timing
+GS_READBACK_STREAM, GS_READBACK_EARLY, GS_READBACK_EARLY_TIMEOUT = 0, 1, 2   # gs_last_readback
 GS_I32, GS_I64, GS_F32, GS_F64, GS_NONE = 0, 1, 2, 3, 4
 GS_OP_SUM, GS_OP_MIN, GS_OP_MAX, GS_OP_COUNT = 0, 1, 2, 3
 STATUS_NAMES = {0: "GS_OK", -1: "GS_EINVAL", -2: "GS_ECAPACITY", -3: "GS_EDEVICE", -4: "GS_ECOMM",
@@ -45,7 +46,7 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_comm_group_create", "gs_comm_group_destroy", "gs_comm_init_group",
            "gs_comm_allreduce_sum_u64", "gs_window_reduce_dist", "gs_window_fold_degree_max_dist",
            "gs_stream_create", "gs_stream_destroy", "gs_stream_append", "gs_stream_watermark", "gs_stream_flush",
-           "gs_stream_poll", "gs_stream_stats", "gs_generate_rmat", "gs_generate_uniform", "gs_generate_zipf", "gs_generate_values", "gs_last_stage_times",
+           "gs_stream_poll", "gs_stream_stats", "gs_generate_rmat", "gs_generate_uniform", "gs_generate_zipf", "gs_generate_values", "gs_last_stage_times", "gs_last_readback",
            "gs_set_max_window_records", "gs_candidates_begin", "gs_candidates_begin_part", "gs_candidates_next", "gs_candidates_next_u32", "gs_candidates_seek",
            "gs_candidates_vertex_range")
 
@@ -228,6 +229,7 @@ def load() -> ctypes.CDLL:
         "gs_generate_zipf": (st, [P, u64, ctypes.c_double, u64, u64, u64, P, P]),
         "gs_generate_values": (st, [P, u64, u64, u64, i32, P]),
         "gs_last_stage_times": (st, [P, ctypes.POINTER(GsStageTimes)]),
+        "gs_last_readback": (st, [P, ctypes.POINTER(i32)]),
         "gs_set_max_window_records": (st, [P, u64]),
         "gs_candidates_begin": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "gs_candidates_begin_part": (st, [P, ctypes.POINTER(GsEdgeBatch), u32, u32, ctypes.POINTER(u64),

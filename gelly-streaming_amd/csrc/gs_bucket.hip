@@ -258,8 +258,12 @@ gs_status bucket_accumulate(gs_ctx* c, Src rs, uint64_t R, uint32_t nb, int64_t 
 }
 
 gs_status bucket_wait(gs_ctx* c) {
-  if (!c->rb_pending) return host_wait(c);
+  if (!c->rb_pending) {
+    c->rb_how = GS_READBACK_STREAM;
+    return host_wait(c);
+  }
   c->rb_pending = false;
+  c->rb_how = GS_READBACK_EARLY;
   volatile uint64_t* h = c->rb_host;
   const uint64_t seq = c->rb_seq;
   const auto t0 = std::chrono::steady_clock::now();
@@ -267,6 +271,7 @@ gs_status bucket_wait(gs_ctx* c) {
     // every 4096 polls: past 2 ms of spinning, wait for the stream instead (a long window, or a fault: its
     // error surfaces there); the block must then be there
     if ((spin & 4095) == 4095 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+      c->rb_how = GS_READBACK_EARLY_TIMEOUT;
       GS_TRY(hip_check(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize"));
       if (h[8] != seq) return set_error(c, GS_EDEVICE, "bucket path: the read-back block never arrived");
       break;

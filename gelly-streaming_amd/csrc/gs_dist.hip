@@ -348,12 +348,14 @@ gs_status gs_window_reduce_partials(gs_ctx* c, const gs_edge_batch* b, int32_t d
                                     gs_partials_out* out) {
   if (!c) return GS_EINVAL;
   if (op < GS_OP_SUM || op > GS_OP_COUNT) return set_error(c, GS_EINVAL, "bad op %d", op);
+  const RbOff sync(c);
   return partials_impl(c, b, dir, op, false, 0, nparts, out);
 }
 
 gs_status gs_window_fold_degree_max_partials(gs_ctx* c, const gs_edge_batch* b, int32_t dir, uint32_t nparts,
                                              gs_partials_out* out) {
   if (!c) return GS_EINVAL;
+  const RbOff sync(c);
   return partials_impl(c, b, dir, 0, true, INT64_MIN, nparts, out);
 }
 
@@ -367,6 +369,7 @@ struct SpMergeSlot {
 gs_status gs_merge_partials(gs_ctx* c, const gs_partial_batch* p, int32_t op, const void* init, gs_vertex_out* out) {
   if (!c) return GS_EINVAL;
   SpMergeSlot slot(c);
+  const RbOff sync(c);
   if (!p || (p->n && (!p->keys || !p->vals))) return set_error(c, GS_EINVAL, "bad gs_partial_batch");
   if (op < GS_OP_SUM || op > GS_OP_COUNT) return set_error(c, GS_EINVAL, "bad op %d", op);
   const int32_t mop = op == GS_OP_COUNT ? GS_OP_SUM : op;            // counts merge by SUM
@@ -378,6 +381,7 @@ gs_status gs_merge_partials(gs_ctx* c, const gs_partial_batch* p, int32_t op, co
 gs_status gs_merge_degree_max_partials(gs_ctx* c, const gs_partial_batch* p, int64_t init_max, gs_degree_out* out) {
   if (!c) return GS_EINVAL;
   SpMergeSlot slot(c);
+  const RbOff sync(c);
   if (!p || (p->n && (!p->keys || !p->vals || !p->vals2))) return set_error(c, GS_EINVAL, "bad gs_partial_batch");
   if (!out || !out->n_out || (out->capacity && (!out->keys || !out->degree || !out->max_neighbor)))
     return set_error(c, GS_EINVAL, "bad gs_degree_out");
@@ -429,6 +433,7 @@ static gs_status dist_impl(gs_ctx* c, const gs_edge_batch* b, int32_t dir, int32
     gs_ctx* c;
     ~OeReset() { c->oe = OwnerEmit{}; }
   } guard{c};
+  const RbOff sync(c);
   return dist_body(c, b, dir, op, init, degmax, init_max, vout, dout);
 }
 static gs_status dist_body(gs_ctx* c, const gs_edge_batch* b, int32_t dir, int32_t op, const void* init, bool degmax,

@@ -85,6 +85,7 @@ uint32_t next_epoch(gs_ctx* c, size_t) {
 gs_status begin_call(gs_ctx* c) {
   ++c->call_seq;   // ends a chunked-candidates session (its sets live in shared workspace)
   c->last_kind = 0;   // the staged output buffers are about to be reused: nothing left to fetch
+  c->rb_how = GS_READBACK_STREAM;   // gs_last_readback: until a bucket_wait of this call says otherwise
   (void)hipGetLastError();
   GS_HIP(hipSetDevice(c->device));
   // the look-back timeout word: cleared unless the previous call's read-back saw it zero (the bucket
@@ -538,6 +539,12 @@ gs_status gs_last_stage_times(const gs_ctx* c, gs_stage_times* out) {
   return GS_OK;
 }
 
+gs_status gs_last_readback(const gs_ctx* c, int32_t* how) {
+  if (!c || !how) return GS_EINVAL;
+  *how = c->rb_how;
+  return GS_OK;
+}
+
 static gs_status finish_vertex_out(gs_ctx* c, gs_vertex_out* out, const int64_t* kd, const void* vd, size_t ob,
                                    uint64_t U, bool direct) {
   *out->n_out = U;
@@ -666,7 +673,8 @@ static gs_status window_chunked(gs_ctx* c, const gs_edge_batch* b, int32_t dir, 
 struct RbAllow {
   gs_ctx* c;
   RbAllow(gs_ctx* c_, bool direct) : c(c_) {
-    c->rb_allow = (c->flags & GS_FLAG_ASYNC_OUTPUT) && direct && c->timing != GS_TIMING_STAGES && !c->oe.nparts;
+    c->rb_allow = (c->flags & GS_FLAG_ASYNC_OUTPUT) && direct && c->timing != GS_TIMING_STAGES && !c->oe.nparts &&
+                  !c->rb_off;
   }
   ~RbAllow() {
     c->rb_allow = false;

@@ -173,6 +173,18 @@ struct gs_ctx {
   uint64_t rb_seq = 0;
   bool rb_allow = false;     // set by the entry point for this window (direct device outputs, not STAGES)
   bool rb_pending = false;   // the last bucket_accumulate left its read-back to bucket_wait
+  int rb_how = 0;            // gs_last_readback: the window's last bucket_wait (GS_READBACK_*)
+  int rb_off = 0;            // > 0: inside another entry point (RbOff): its windows keep the synchronous read-back
+};
+
+// GS_FLAG_ASYNC_OUTPUT covers gs_window_reduce / _fold / _fold_degree_max called by the user; the entry points
+// that run those windows as a step of their own (partials, merges, the exchange) are unchanged by the flag
+struct RbOff {
+  gs_ctx* c;
+  explicit RbOff(gs_ctx* cc) : c(cc) { ++c->rb_off; }
+  ~RbOff() { --c->rb_off; }
+  RbOff(const RbOff&) = delete;
+  RbOff& operator=(const RbOff&) = delete;
 };
 
 namespace gs {

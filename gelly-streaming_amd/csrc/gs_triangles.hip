@@ -695,6 +695,7 @@ __global__ __launch_bounds__(UO_BLOCK) void k_tri_uo_count(const uint64_t* __res
   const uint64_t vmask = (1ull << B) - 1;
   if (hist) {
     for (int i = threadIdx.x; i < NW * 8 * RADIX; i += UO_BLOCK) (&s_h[0][0][0])[i] = 0;
+    __syncthreads();   // every wave's table is zeroed by all threads: before any wave adds to its own
   }
   for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // block-uniform
     const uint64_t t0 = tile * UO_TILE;

@@ -184,6 +184,13 @@ class Engine:
         self._check(self._L.gs_last_stage_times(self.ctx, ctypes.byref(t)))
         return t
 
+    def last_readback(self) -> int:
+        """gs_last_readback: how the last reduce / fold / fold_degree_max window got its sizes back
+        (L.GS_READBACK_STREAM / _EARLY / _EARLY_TIMEOUT)."""
+        how = ctypes.c_int32(0)
+        self._check(self._L.gs_last_readback(self.ctx, ctypes.byref(how)))
+        return how.value
+
     @staticmethod
     def stage_times_of(t) -> StageTimes:
         if isinstance(t, StageTimes):
@@ -264,7 +271,7 @@ class Engine:
             v = None if op == L.GS_OP_COUNT else val
             key = (id(src), id(dst), id(v), int(direction), int(op), id(out[0]), id(out[1]))
             ptrs = (src.data_ptr(), dst.data_ptr(), v.data_ptr() if v is not None else 0, out[0].data_ptr(),
-                    out[1].data_ptr(), src.numel())
+                    out[1].data_ptr(), src.numel(), dst.numel(), v.numel() if v is not None else 0)
             args = getattr(self, "_args", None)
             if args is None:
                 args = self._args = {}

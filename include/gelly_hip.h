@@ -614,6 +614,14 @@ GS_API gs_status gs_last_stage_times(const gs_ctx* ctx, gs_stage_times* out);
 #define GS_TIMING_DOMINANT 1
 #define GS_TIMING_STAGES 2
 GS_API gs_status gs_set_timing(gs_ctx* ctx, int32_t level);
+/* How the last reduce / fold / degree-fold window of the ctx got its sizes back (diagnostics): the last
+ * read-back of that window.  GS_FLAG_ASYNC_OUTPUT windows into device outputs, at a timing level below
+ * GS_TIMING_STAGES, return on the block the emit kernel writes into pinned host memory; every other
+ * window waits for the stream.  Each window call starts from GS_READBACK_STREAM. */
+#define GS_READBACK_STREAM 0         /* the call waited for the stream (host_wait) */
+#define GS_READBACK_EARLY 1          /* returned on the emit's pinned read-back block */
+#define GS_READBACK_EARLY_TIMEOUT 2  /* early block requested, the 2 ms spin expired, waited for the stream */
+GS_API gs_status gs_last_readback(const gs_ctx* ctx, int32_t* how);
 
 #ifdef __cplusplus
 }
