@@ -40,7 +40,7 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_window_triangles_part", "gs_window_count_candidates", "gs_tri_dist_range", "gs_tri_dist_degrees",
            "gs_tri_dist_orient", "gs_tri_dist_route", "gs_tri_dist_build", "gs_tri_dist_plan", "gs_tri_dist_need", "gs_tri_dist_serve",
            "gs_tri_dist_assemble", "gs_tri_dist_count", "gs_window_triangles_selfpair",
-           "gs_window_triangles_dist", "gs_window_components",
+           "gs_window_triangles_dist", "gs_window_components", "gs_window_bipartite",
            "gs_parse_edges_text", "gs_fetch_last_output", "gs_fetch_last_degree_output", "gs_owner_of", "gs_window_reduce_partials", "gs_window_fold_degree_max_partials",
            "gs_merge_partials", "gs_merge_degree_max_partials", "gs_comm_unique_id", "gs_comm_init", "gs_comm_destroy",
            "gs_comm_group_create", "gs_comm_group_destroy", "gs_comm_init_group",
@@ -110,6 +110,15 @@ class GsPartialsOut(ctypes.Structure):
 
 class GsPartialBatch(ctypes.Structure):
     _fields_ = [("keys", P), ("vals", P), ("vals2", P), ("n", u64), ("val_dtype", i32), ("mem", i32)]
+
+
+class GsSignedBatch(ctypes.Structure):   # gs_signed_batch: a previous bipartiteness state
+    _fields_ = [("keys", P), ("labels", P), ("signs", P), ("n", u64), ("mem", i32), ("failed", i32)]
+
+
+class GsSignedOut(ctypes.Structure):
+    _fields_ = [("keys", P), ("labels", P), ("signs", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)),
+                ("success", ctypes.POINTER(i32)), ("mem", i32), ("reserved", i32)]
 
 
 class GsStreamConfig(ctypes.Structure):
@@ -195,6 +204,8 @@ def load() -> ctypes.CDLL:
         "gs_window_triangles_selfpair": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(u64)]),
         "gs_window_components": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsPartialBatch),
                                       ctypes.POINTER(GsVertexOut)]),
+        "gs_window_bipartite": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsSignedBatch),
+                                     ctypes.POINTER(GsSignedOut)]),
         "gs_window_triangles_dist": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(u64), ctypes.POINTER(i32),
                                           ctypes.POINTER(i32)]),
         "gs_window_count_candidates": (st, [P, ctypes.POINTER(GsPairBatch), ctypes.POINTER(u64), ctypes.POINTER(i32),

@@ -16,7 +16,7 @@
 //      smallest vertex (the IDs are order-preserving), the canonical label of the partition
 // Which vertex the reference's DisjointSet keeps as a root depends on HashMap iteration order; the
 // partition (what ConnectedComponentsTest and DisjointSet.toString observe) does not.
-#include "gs_ops.hpp"
+#include "gs_cc_common.hpp"
 
 namespace gs {
 
@@ -93,27 +93,8 @@ __global__ __launch_bounds__(256) void k_cc_emit(uint32_t* parent, const int64_t
   }
 }
 
-__global__ __launch_bounds__(256) void k_cc_concat(const int64_t* __restrict__ a, const int64_t* __restrict__ b,
-                                                   uint64_t n, int64_t* __restrict__ oa, int64_t* __restrict__ ob) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    oa[i] = a[i];
-    ob[i] = b[i];
-  }
-}
-
-// ---- direct ids (the window's ids span <= CC_DIRECT_BITS bits: no relabel) ---------------------------
-constexpr uint32_t CC_DIRECT_BITS = 28;
-
-// OR of (id ^ k0) over both columns, k0 = *k0p (the first id of the call)
-__global__ __launch_bounds__(256) void k_cc_mask(const int64_t* __restrict__ a, const int64_t* __restrict__ b, uint64_t n,
-                                                 const int64_t* __restrict__ k0p, unsigned long long* __restrict__ mask) {
-  const uint64_t k0 = (uint64_t)*k0p;
-  uint64_t m = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-    m |= ((uint64_t)a[i] ^ k0) | ((uint64_t)b[i] ^ k0);
-  m = wave_or(m);
-  if ((threadIdx.x & 63) == 0 && m) atomicOr(mask, (unsigned long long)m);
-}
+// ---- direct ids (the window's ids span <= CC_DIRECT_BITS bits: no relabel; k_cc_mask, k_cc_flags and
+// k_cc_concat are in gs_cc_common.hpp) ------------------------------------------------------------------
 
 // unions over (a[e] ^ key_xor, b[e] ^ key_xor); a self-loop marks its vertex present (it has no link)
 __global__ __launch_bounds__(256) void k_cc_hook_ids(const int64_t* __restrict__ a, const int64_t* __restrict__ b,
@@ -168,26 +149,7 @@ __global__ __launch_bounds__(256) void k_cc_hook_ids_phase(const int64_t* __rest
   }
 }
 
-// the giant tree after phase 0: the most frequent root among the parents of 1024 sampled edges' sources
-// (one block; any root would be correct -- the bits only let edges skip that are joined already)
-// (compact ids: at != nullptr, the sources at[2e] instead of a[e] ^ key_xor)
-__global__ __launch_bounds__(1024) void k_cc_giant(const int64_t* __restrict__ a, const uint32_t* __restrict__ at,
-                                                   uint64_t n, uint64_t key_xor, const uint32_t* __restrict__ parent,
-                                                   uint32_t* __restrict__ giant) {
-  __shared__ uint32_t s_r[1024];
-  __shared__ unsigned long long s_best;
-  const uint32_t t = threadIdx.x;
-  const uint64_t e = (uint64_t)t * (n / 1024);
-  s_r[t] = parent[at ? at[2 * e] : (uint32_t)((uint64_t)a[e] ^ key_xor)];
-  if (t == 0) s_best = 0;
-  __syncthreads();
-  const uint32_t mine = s_r[t];
-  uint32_t c = 0;
-  for (int i = 0; i < 1024; ++i) c += s_r[i] == mine ? 1u : 0u;
-  atomicMax(&s_best, ((unsigned long long)c << 32) | mine);
-  __syncthreads();
-  if (t == 0) *giant = (uint32_t)s_best;
-}
+// (k_cc_giant, the giant tree after phase 0, is in gs_cc_common.hpp)
 // bit v of gbits: parent[v] is the giant root (after the compression, parent[v] is v's root)
 __global__ __launch_bounds__(256) void k_cc_gbits(const uint32_t* __restrict__ parent, uint32_t V,
                                                   const uint32_t* __restrict__ giant, uint32_t* __restrict__ gbits) {
@@ -210,10 +172,6 @@ __global__ __launch_bounds__(256) void k_cc_compress(uint32_t* parent, uint32_t 
     mark[i] = 1;
     mark[r] = 1;
   }
-}
-
-__global__ __launch_bounds__(256) void k_cc_flags(const uint8_t* __restrict__ mark, uint32_t V, uint64_t* __restrict__ f) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < V; i += gridDim.x * 256u) f[i] = mark[i];
 }
 
 __global__ __launch_bounds__(256) void k_cc_emit_ids(const uint32_t* __restrict__ parent, const uint8_t* __restrict__ mark,
@@ -314,7 +272,7 @@ gs_status gs_window_components(gs_ctx* c, const gs_edge_batch* b, const gs_parti
           GS_TRY(ensure(c, c->cc[3], (size_t)(V + 31) / 32 * 4 + 64));
           gbits = c->cc[3].as<uint32_t>();
           uint32_t* giant = gbits + (V + 31) / 32;
-          hipLaunchKernelGGL(k_cc_giant, dim3(1), dim3(1024), 0, c->stream, big.a, (const uint32_t*)nullptr, big.n, key_xor,
+          hipLaunchKernelGGL(k_cc_giant<0>, dim3(1), dim3(1024), 0, c->stream, big.a, (const uint32_t*)nullptr, big.n, key_xor,
                              parent, giant);
           hipLaunchKernelGGL(k_cc_gbits, dim3((unsigned)std::min<uint64_t>(((V + 31) / 32 + 255) / 256, 16384)), dim3(256),
                              0, c->stream, parent, V, giant, gbits);
@@ -399,7 +357,7 @@ gs_status gs_window_components(gs_ctx* c, const gs_edge_batch* b, const gs_parti
         GS_TRY(ensure(c, c->cc[3], (size_t)(U + 31) / 32 * 4 + 64));
         gbits = c->cc[3].as<uint32_t>();
         uint32_t* giant = gbits + (U + 31) / 32;
-        hipLaunchKernelGGL(k_cc_giant, dim3(1), dim3(1024), 0, c->stream, (const int64_t*)nullptr, at, N, 0ull, parent, giant);
+        hipLaunchKernelGGL(k_cc_giant<0>, dim3(1), dim3(1024), 0, c->stream, (const int64_t*)nullptr, at, N, 0ull, parent, giant);
         hipLaunchKernelGGL(k_cc_gbits, dim3((unsigned)std::min<uint64_t>(((U + 31) / 32 + 255) / 256, 16384)), dim3(256), 0,
                            c->stream, parent, (uint32_t)U, giant, gbits);
       }

@@ -195,7 +195,7 @@ class Engine:
     def stage_times_of(t) -> StageTimes:
         if isinstance(t, StageTimes):
             return t
-        launched = 5 if t.path in (2, 3) else 3 if t.path == 4 else \
+        launched = 5 if t.path in (2, 3) else 3 if t.path in (4, 5) else \
             t.sort_passes + (3 if t.path == 1 else 1 if t.fused_last else 0)
         return StageTimes(t.keyinfo_ms, t.sort_ms, t.reduce_ms, t.total_ms, t.sort_passes, t.key_bits, t.records,
                           t.vertices, list(t.pass_ms)[:launched], t.key_bytes, t.payload_bytes,
@@ -638,6 +638,39 @@ class Engine:
                                                  ctypes.byref(out)))
         U = n_out.value
         return keys[:U], labels[:U]
+
+    # -- BipartitenessCheck (gs_bipartite.hip) --------------------------------------------------------
+    def bipartite(self, src, dst, prev=None):
+        """gs_window_bipartite: the running bipartiteness state after this window's edges; prev = a previous
+        return value or None.  Returns (success, vertices ascending, smallest vertex of each one's component,
+        sign: 1 = on that vertex's side), the arrays on the columns' side (device tensors / numpy) and empty
+        when success is False (the state (false,{}), which every later window keeps)."""
+        b, keep, dev = self._batch(src, dst, None)
+        m, failed, pk, pl, ps = 0, 0, None, None, None
+        if prev is not None:
+            ok, pk, pl, ps = prev
+            failed, m = int(not ok), (len(pk) if ok else 0)
+        pb = None
+        if failed:
+            pb = L.GsSignedBatch(None, None, None, 0, L.GS_MEM_HOST, 1)
+        elif m:
+            if dev:
+                assert _is_torch(pk) and pk.is_cuda, "the previous state lives where the columns do"
+                pk, pl, ps = pk.contiguous(), pl.contiguous(), ps.contiguous()
+            else:
+                pk, pl = np.ascontiguousarray(pk, np.int64), np.ascontiguousarray(pl, np.int64)
+                ps = np.ascontiguousarray(ps, np.uint8)
+            pb = L.GsSignedBatch(_ptr(pk), _ptr(pl), _ptr(ps), m, L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        cap = 0 if failed else 2 * b.n + m + 1
+        keys, labels = self._empty(dev, cap, np.int64), self._empty(dev, cap, np.int64)
+        signs = self._empty(dev, cap, np.uint8)
+        n_out, success = ctypes.c_uint64(0), ctypes.c_int32(0)
+        out = L.GsSignedOut(_ptr(keys), _ptr(labels), _ptr(signs), cap, ctypes.pointer(n_out), ctypes.pointer(success),
+                            L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        self._check(self._L.gs_window_bipartite(self.ctx, ctypes.byref(b), ctypes.byref(pb) if pb is not None else None,
+                                                ctypes.byref(out)))
+        U = n_out.value
+        return bool(success.value), keys[:U], labels[:U], signs[:U]
 
     # -- multi-GPU keyBy halves (gs_dist.hip) --------------------------------------------------------
     def reduce_partials(self, src, dst, val, direction, op, nparts: int):

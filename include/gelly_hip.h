@@ -455,6 +455,43 @@ GS_API gs_status gs_window_fold_degree_max_dist(gs_ctx* ctx, const gs_edge_batch
 GS_API gs_status gs_window_components(gs_ctx* ctx, const gs_edge_batch* window, const gs_partial_batch* prev,
                                       gs_vertex_out* out);
 
+/* BipartitenessCheck over a window stream (library/BipartitenessCheck.java:40-136 through
+ * WindowGraphAggregation.java:47-65; state type example/util/Candidates.java:26-196): the running
+ * Candidates state after this window -- the previous state's (vertex, label, sign) rows (NULL, or n = 0
+ * and not failed, for the first window) merged with the window's edges (direction and values ignored:
+ * NullValue in the reference).  The state is canonical: *success = 1 iff the graph of every edge seen so
+ * far has no odd cycle (a self-loop only makes its vertex present, as edgeToCandidate(v, v) does:
+ * BipartitenessCheck.java:57-64 with Candidates.java:64-68); then out holds every vertex seen so far,
+ * ascending, with the smallest vertex of its component (I64 label) and sign = 1 iff the vertex is on that
+ * label's side.  Otherwise *success = 0 and *n_out = 0 -- Candidates.fail() :193-195 -- and the state
+ * stays failed: with prev->failed the call returns that at once (Candidates.java:78-80).  This is what
+ * Candidates.merge :76-138 computes when the edges arrive in ascending order of min(src, dst); in other
+ * orders merge depends on the order (:117-122 keeps a retired component, :129 drops the result of fail(),
+ * :91-94 skips components with equal vertex sets whatever their signs) and the canonical state does not.
+ * An empty window returns prev's rows.  capacity < the vertices seen so far: GS_ECAPACITY with *n_out =
+ * the rows needed (m + 2n always suffices).  Feed the output back as `prev` for the next window
+ * (transientState = false). */
+typedef struct gs_signed_batch {   /* a previous bipartiteness state */
+  const int64_t* keys;
+  const int64_t* labels;
+  const uint8_t* signs;
+  uint64_t n;
+  int32_t mem;      /* gs_mem of keys / labels / signs */
+  int32_t failed;   /* failed != 0: the state is (false,{}) */
+} gs_signed_batch;
+typedef struct gs_signed_out {
+  int64_t* keys;
+  int64_t* labels;
+  uint8_t* signs;
+  uint64_t capacity;
+  uint64_t* n_out;
+  int32_t* success;
+  int32_t mem;
+  int32_t reserved;
+} gs_signed_out;
+GS_API gs_status gs_window_bipartite(gs_ctx* ctx, const gs_edge_batch* window, const gs_signed_batch* prev,
+                                     gs_signed_out* out);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;
@@ -593,7 +630,10 @@ typedef struct gs_stage_times {
                               3: window triangles (pass_ms[0..4] = symmetric keys + sort, unique,
                                  rows + orientation, light count, heavy count; records = unique
                                  adjacency entries, vertices = vertices with edges, partials = hash
-                                 probes of the counting step, sort_passes = LSD passes)          */
+                                 probes of the counting step, sort_passes = LSD passes);
+                              4: connected components, 5: bipartiteness check (pass_ms[0..2] = staging
+                                 + ids, union-find + compression, labels; records = window edges +
+                                 state rows)                                                     */
   uint32_t packed;         /* path 2: 1 = 4-byte packed partition records (k_dp_scatter_pack)    */
   uint32_t speculative;    /* path 2: 0 = per-tile histogram + offsets (k_dp_hist);
                               1 = speculative partition (regions from the previous window's counts,

@@ -212,6 +212,33 @@ JNIEXPORT jlong JNI_FN(windowComponents)(JNIEnv* env, jclass cls, jlong ctx, job
   return rows_or_throw(env, c, gs_window_components(c, &b, m ? &prev : NULL, &o), n_out, "gs_window_components");
 }
 
+/* {rows written or -(rows needed) on GS_ECAPACITY, success}; failed != 0: the previous state is (false,{}) */
+JNIEXPORT jlongArray JNI_FN(windowBipartite)(JNIEnv* env, jclass cls, jlong ctx, jobject src, jobject dst, jlong n,
+                                             jobject pk, jobject pl, jobject ps, jlong m, jint failed, jobject ok,
+                                             jobject ol, jobject os, jlong cap) {
+  gs_ctx* c = (gs_ctx*)(intptr_t)ctx;
+  gs_edge_batch b = batch(env, src, dst, NULL, n, GS_NONE);
+  gs_signed_batch prev;
+  memset(&prev, 0, sizeof prev);
+  prev.keys = (const int64_t*)addr(env, pk);
+  prev.labels = (const int64_t*)addr(env, pl);
+  prev.signs = (const uint8_t*)addr(env, ps);
+  prev.n = (uint64_t)m;
+  prev.mem = GS_MEM_HOST;
+  prev.failed = failed;
+  uint64_t n_out = 0;
+  int32_t success = 0;
+  gs_signed_out o = {(int64_t*)addr(env, ok), (int64_t*)addr(env, ol), (uint8_t*)addr(env, os), (uint64_t)cap, &n_out,
+                     &success, GS_MEM_HOST, 0};
+  gs_status s = gs_window_bipartite(c, &b, (m || failed) ? &prev : NULL, &o);
+  if (s != GS_OK && s != GS_ECAPACITY) {
+    throw_status(env, c, s, "gs_window_bipartite");
+    return NULL;
+  }
+  const jlong r[2] = {s == GS_OK ? (jlong)n_out : -(jlong)n_out, (jlong)success};
+  return long_array(env, r, 2);
+}
+
 /* ---- gs_stream_*: the stream keeps its ctx (one per operator subtask) -------------------------------- */
 typedef struct {
   gs_ctx* ctx;

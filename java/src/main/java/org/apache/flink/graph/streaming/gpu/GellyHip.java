@@ -149,6 +149,19 @@ public final class GellyHip {
 	static native long windowComponents(long ctx, ByteBuffer src, ByteBuffer dst, long n, ByteBuffer prevKeys,
 			ByteBuffer prevLabels, long m, ByteBuffer outKeys, ByteBuffer outLabels, long capacity);
 
+	/**
+	 * gs_window_bipartite: BipartitenessCheck (library/BipartitenessCheck.java:40-136, state
+	 * example/util/Candidates.java) over one window: the previous state's m (vertex, label, sign) rows --
+	 * or prevFailed != 0 for the state (false,{}) -- merged with the window's n edges into out: every
+	 * vertex seen so far, ascending, with its component's smallest vertex and sign 1 iff it is on that
+	 * vertex's side (one byte per sign).  Returns {rows, success}: rows written, or -(rows needed) when
+	 * capacity is short (m + 2n always suffices); success 0 = an odd cycle, no rows, and every later
+	 * window's state is failed too.
+	 */
+	static native long[] windowBipartite(long ctx, ByteBuffer src, ByteBuffer dst, long n, ByteBuffer prevKeys,
+			ByteBuffer prevLabels, ByteBuffer prevSigns, long m, int prevFailed, ByteBuffer outKeys,
+			ByteBuffer outLabels, ByteBuffer outSigns, long capacity);
+
 	/* ---- the window-buffer operator (gs_stream_*): event-time tumbling windows ------------------------ */
 	static native long streamCreate(long ctx, long windowMs, int kind, int direction, int op, int valDtype,
 			int watermarkMode, int staging, ByteBuffer init, long initMax, long maxWindowEdges, int lateMode);

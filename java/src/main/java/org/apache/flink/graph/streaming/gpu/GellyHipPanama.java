@@ -42,6 +42,14 @@ public final class GellyHipPanama implements AutoCloseable {
 			ADDRESS.withName("a"), ADDRESS.withName("b"), ADDRESS.withName("is_candidate"),
 			JAVA_LONG.withName("capacity"), ADDRESS.withName("n_out"), JAVA_INT.withName("mem"),
 			JAVA_INT.withName("reserved"));
+	/* gs_signed_batch, gs_signed_out: a bipartiteness state (gs_window_bipartite) */
+	static final StructLayout SIGNED_BATCH = MemoryLayout.structLayout(
+			ADDRESS.withName("keys"), ADDRESS.withName("labels"), ADDRESS.withName("signs"), JAVA_LONG.withName("n"),
+			JAVA_INT.withName("mem"), JAVA_INT.withName("failed"));
+	static final StructLayout SIGNED_OUT = MemoryLayout.structLayout(
+			ADDRESS.withName("keys"), ADDRESS.withName("labels"), ADDRESS.withName("signs"),
+			JAVA_LONG.withName("capacity"), ADDRESS.withName("n_out"), ADDRESS.withName("success"),
+			JAVA_INT.withName("mem"), JAVA_INT.withName("reserved"));
 
 	private static final Linker LINKER = Linker.nativeLinker();
 	private static final SymbolLookup LIB = SymbolLookup.libraryLookup("libgellyhip.so", Arena.global());
@@ -67,7 +75,9 @@ public final class GellyHipPanama implements AutoCloseable {
 			FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
 	private static final MethodHandle FETCH_LAST_OUTPUT = fn("gs_fetch_last_output",
 			FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
-	private static final MethodHandle SET_TIMING = fn("gs_set_timing", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
+	private static final MethodHandle WINDOW_BIPARTITE = fn("gs_window_bipartite",
+			FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+	private static final MethodHandle SET_TIMING =fn("gs_set_timing", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
 
 	private final Arena arena = Arena.ofConfined();
 	private final MemorySegment ctx;
@@ -204,5 +214,38 @@ public final class GellyHipPanama implements AutoCloseable {
 		o.set(JAVA_INT, 40, GellyHip.GS_MEM_HOST);
 		check((int) CANDIDATES_NEXT.invokeExact(ctx, o, first, done), "gs_candidates_next");
 		return new long[] {nOut.get(JAVA_LONG, 0), first.get(JAVA_LONG, 0), done.get(JAVA_INT, 0)};
+	}
+
+	/**
+	 * gs_window_bipartite (BipartitenessCheck, library/BipartitenessCheck.java:40-136): the previous state's m
+	 * (vertex, label, sign) rows -- or prevFailed for the state (false,{}) -- merged with the window's n edges:
+	 * {rows written or -(rows needed), success}.
+	 */
+	public long[] windowBipartite(MemorySegment src, MemorySegment dst, long n, MemorySegment prevKeys,
+			MemorySegment prevLabels, MemorySegment prevSigns, long m, boolean prevFailed, MemorySegment keys,
+			MemorySegment labels, MemorySegment signs, long capacity) throws Throwable {
+		final MemorySegment nOut = arena.allocate(JAVA_LONG), success = arena.allocate(JAVA_INT);
+		MemorySegment prev = MemorySegment.NULL;
+		if (m > 0 || prevFailed) {
+			prev = arena.allocate(SIGNED_BATCH);
+			prev.set(ADDRESS, 0, m > 0 ? prevKeys : MemorySegment.NULL);
+			prev.set(ADDRESS, 8, m > 0 ? prevLabels : MemorySegment.NULL);
+			prev.set(ADDRESS, 16, m > 0 ? prevSigns : MemorySegment.NULL);
+			prev.set(JAVA_LONG, 24, m);
+			prev.set(JAVA_INT, 32, GellyHip.GS_MEM_HOST);
+			prev.set(JAVA_INT, 36, prevFailed ? 1 : 0);
+		}
+		final MemorySegment o = arena.allocate(SIGNED_OUT);
+		o.set(ADDRESS, 0, keys);
+		o.set(ADDRESS, 8, labels);
+		o.set(ADDRESS, 16, signs);
+		o.set(JAVA_LONG, 24, capacity);
+		o.set(ADDRESS, 32, nOut);
+		o.set(ADDRESS, 40, success);
+		o.set(JAVA_INT, 48, GellyHip.GS_MEM_HOST);
+		final int st = (int) WINDOW_BIPARTITE.invokeExact(ctx, batch(src, dst, null, n, GellyHip.GS_NONE), prev, o);
+		if (st != GellyHip.GS_ECAPACITY) check(st, "gs_window_bipartite");
+		final long rows = nOut.get(JAVA_LONG, 0);
+		return new long[] {st == GellyHip.GS_ECAPACITY ? -rows : rows, success.get(JAVA_INT, 0)};
 	}
 }

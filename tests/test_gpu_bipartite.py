@@ -1,0 +1,201 @@
+"""GPU: BipartitenessCheck (gs_window_bipartite; library/BipartitenessCheck.java on WindowGraphAggregation)
+against the canonical state of tests/bipartite_cpu.py (a sequential parity union-find, pinned to the
+reference's Candidates in tests/test_bipartite_host.py): the success flag and, per vertex seen so far, the
+smallest vertex of its component and its side -- bit-exact."""
+import ctypes
+import functools
+import json
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+from bipartite_cpu import canonical
+
+pytestmark = pytest.mark.gpu
+FIX = json.loads((Path(__file__).parent / "golden" / "bipartiteness_fixtures.json").read_text())
+
+
+def _np(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _same(got, want):
+    assert bool(got[0]) == bool(want[0])
+    for g, w in zip(got[1:], want[1:]):
+        g = _np(g)
+        assert g.dtype == w.dtype and np.array_equal(g, w)
+
+
+def _failed(got):
+    assert got[0] is False and all(len(x) == 0 for x in got[1:])
+
+
+def _dev(*cols):
+    return tuple(torch.from_numpy(np.array(c)).cuda() for c in cols)   # a copy: the shared graphs are read-only
+
+
+@pytest.mark.parametrize("case", ["BipartitenessCheckTest", "NonBipartitnessCheckTest"])
+def test_reference_fixtures_through_the_api(pkg, engine, case):
+    """graph.aggregate(new BipartitenessCheck<>(500)): one Candidates record, the reference's line."""
+    fx = FIX[case]
+    e = np.array(fx["edges"], dtype=np.int64)
+    env = pkg.StreamExecutionEnvironment.getExecutionEnvironment()
+    g = pkg.SimpleEdgeStream(pkg.EdgeColumns(e[:, 0], e[:, 1]), env)
+    out = g.aggregate(pkg.BipartitenessCheck(fx["merge_window_ms"])).collect()
+    assert len(out) == 1 and isinstance(out[0], pkg.Candidates)
+    assert str(out[0]) == fx["expected"]
+
+
+# ---- R-MAT made bipartite (src * 2, dst * 2 + 1: it keeps R-MAT's skew), below and above the 65536-record
+# switch to the two-phase unions, on the direct path (plain ids) and the relabel path (64-bit, negative ids)
+GRAPHS = {"s12": (12, 5_000, 0x5EEDB0), "s16": (16, 300_000, 0x5EEDB1)}
+
+
+@functools.lru_cache(maxsize=None)
+def _graph(name, sparse):
+    import __graft_entry__ as ge
+    scale, n, seed = GRAPHS[name]
+    s, d = ge.load_oracle().gen_rmat(scale, n, seed)
+    s, d = s * 2, d * 2 + 1
+    if sparse:
+        s, d = s * 7_919_000_003 - (1 << 61), d * 7_919_000_003 - (1 << 61)
+    want = canonical(s, d)
+    assert want[0]
+    for a in (s, d) + want[1:]:
+        a.setflags(write=False)
+    return s, d, want
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["direct", "relabel"])
+@pytest.mark.parametrize("name", list(GRAPHS))
+def test_bipartite_rmat(engine, name, sparse):
+    s, d, want = _graph(name, sparse)
+    _same(engine.bipartite(*_dev(s, d)), want)
+    _same(engine.bipartite(s, d), want)   # host columns
+    t = engine.stage_times()
+    assert t.path == 5 and t.records == len(s) and t.vertices == len(want[1])
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["direct", "relabel"])
+@pytest.mark.parametrize("name", list(GRAPHS))
+def test_one_bad_edge_fails_the_window(engine, name, sparse):
+    """One edge between two vertices on the same side of the largest component, at a random position: the
+    single conflict must be seen wherever it lands among the concurrent unions."""
+    s, d, (_, v, lab, sign) = _graph(name, sparse)
+    labels, counts = np.unique(lab, return_counts=True)
+    side = v[(lab == labels[np.argmax(counts)]) & (sign == 1)]
+    rng = np.random.default_rng(GRAPHS[name][2] + sparse)
+    a, b = rng.choice(side, 2, replace=False)
+    at = int(rng.integers(0, len(s) + 1))
+    s2, d2 = np.insert(s, at, a), np.insert(d, at, b)
+    _failed(engine.bipartite(*_dev(s2, d2)))
+    _failed(engine.bipartite(s2, d2))
+
+
+@pytest.mark.parametrize("kind", ["path", "even_cycle", "odd_cycle"])
+def test_long_parity_chains(engine, kind):
+    rng = np.random.default_rng(11)
+    nv = 200_001 if kind == "odd_cycle" else 200_000
+    p = rng.permutation(nv).astype(np.int64)
+    s, d = p[:-1].copy(), p[1:].copy()
+    if kind != "path":
+        s, d = np.append(s, p[-1]), np.append(d, p[0])
+    o = rng.permutation(len(s))
+    s, d = s[o], d[o]
+    got = engine.bipartite(*_dev(s, d))
+    if kind == "odd_cycle":
+        _failed(got)
+        return
+    _same(got, canonical(s, d))
+    sign = _np(got[3])
+    assert np.all(sign[p[:-1]] != sign[p[1:]]) and np.all(_np(got[2]) == 0)   # sides alternate along the path
+
+
+def test_self_loops_and_repeats(engine):
+    rng = np.random.default_rng(12)
+    s = rng.integers(0, 2_500, 20_000).astype(np.int64) * 2
+    d = rng.integers(0, 2_500, 20_000).astype(np.int64) * 2 + 1
+    loop = rng.random(20_000) < 0.3
+    d = np.where(loop, s, d)
+    s, d = np.concatenate([s, d, s]), np.concatenate([d, s, d])   # every edge reversed and duplicated too
+    o = rng.permutation(len(s))
+    s, d = s[o], d[o]
+    want = canonical(s, d)
+    got = engine.bipartite(*_dev(s, d))
+    _same(got, want)
+    only_loops = np.setdiff1d(s[s == d], np.concatenate([s[s != d], d[s != d]]))
+    assert len(only_loops)
+    at = np.searchsorted(want[1], only_loops)
+    assert np.array_equal(_np(got[2])[at], only_loops) and np.all(_np(got[3])[at] == 1)   # singletons, sign true
+    _same(engine.bipartite(s, d), want)
+
+
+def test_accumulation_over_windows(engine, oracle):
+    """transientState = false: window k's state = window k-1's state merged with window k's edges; a failed
+    state stays failed; an empty window leaves a good state as it is."""
+    s, d = oracle.gen_rmat(15, 80_000, 0x5EEDB2)
+    s, d = s * 2, d * 2 + 1
+    state_g = state_c = None
+    for w in range(4):
+        ws, wd = s[w * 20_000:(w + 1) * 20_000], d[w * 20_000:(w + 1) * 20_000]
+        state_c = canonical(ws, wd, state_c)
+        state_g = engine.bipartite(*_dev(ws, wd), state_g)
+        _same(state_g, state_c)
+    _same(state_g, canonical(s, d))   # = the state of all the edges
+    empty = np.empty(0, np.int64)
+    _same(engine.bipartite(*_dev(empty, empty), state_g), state_c)
+    _same(engine.bipartite(empty, empty, tuple(_np(x) for x in state_g)), state_c)
+    # a fifth window whose only edge closes an odd cycle through vertices of windows 0 and 2
+    _, v, lab, sign = state_c
+    big = np.bincount(np.searchsorted(v, lab)).argmax()
+    in0 = np.isin(v, np.concatenate([s[:20_000], d[:20_000]]))
+    in2 = np.isin(v, np.concatenate([s[40_000:60_000], d[40_000:60_000]]))
+    side = (lab == v[big]) & (sign == 1)
+    a = v[side & in0][0]
+    b = v[side & in2 & (v != a)][-1]
+    bad = engine.bipartite(*_dev(np.array([a]), np.array([b])), state_g)
+    _failed(bad)
+    assert not canonical([a], [b], state_c)[0]
+    _failed(engine.bipartite(*_dev(s[:100], d[:100]), bad))   # a sixth, harmless window: still failed
+    _failed(engine.bipartite(s[:100], d[:100], bad))
+
+
+def test_capacity_error_reports_the_rows_needed(pkg, engine):
+    from gelly_streaming_amd import _lib as L
+    s, d, want = _graph("s12", False)
+    U = len(want[1])
+    for cap in (U - 1, U):
+        keys, labels, signs = np.empty(U, np.int64), np.empty(U, np.int64), np.empty(U, np.uint8)
+        n_out, success = ctypes.c_uint64(0), ctypes.c_int32(-1)
+        b = L.GsEdgeBatch(s.ctypes.data, d.ctypes.data, None, len(s), L.GS_NONE, L.GS_MEM_HOST, 0)
+        out = L.GsSignedOut(keys.ctypes.data, labels.ctypes.data, signs.ctypes.data, cap, ctypes.pointer(n_out),
+                            ctypes.pointer(success), L.GS_MEM_HOST, 0)
+        st = engine._L.gs_window_bipartite(engine.ctx, ctypes.byref(b), None, ctypes.byref(out))
+        assert n_out.value == U and success.value == 1
+        assert st == (L.GS_ECAPACITY if cap < U else L.GS_OK)
+    _same((True, keys, labels, signs), want)
+    assert engine._L.gs_window_bipartite(engine.ctx, ctypes.byref(b), None, None) == L.GS_EINVAL
+
+
+def test_partials_at_parallelism(pkg, oracle):
+    """Environment parallelism 4 (GraphAggregation.java:103-116): one Candidates per non-empty partition's
+    partial, each the canonical state over the previous state and that partition's records (arrival index
+    mod 4)."""
+    s, d = oracle.gen_rmat(12, 6_000, 0x5EEDB3)
+    s, d = s * 2, d * 2 + 1
+    ts = (np.arange(len(s)) * 2).astype(np.int64)   # windows of 500 records (1000 ms)
+    env = pkg.StreamExecutionEnvironment()
+    env.setParallelism(4)
+    out = pkg.SimpleEdgeStream(pkg.EdgeColumns(s, d, None, ts), env).aggregate(pkg.BipartitenessCheck(1000))
+    assert len(out.windows) == 4 * (len(s) // 500)
+    state, i = None, 0
+    for w0 in range(0, len(s), 500):
+        for k in range(4):
+            sel = np.arange(w0, w0 + 500)
+            sel = sel[sel % 4 == k]
+            state = canonical(s[sel], d[sel], state)
+            tag, recs = out.windows[i].columns
+            assert tag == "records" and len(recs) == 1 and recs[0] == pkg.Candidates(*state)
+            i += 1
+    assert out.windows[-1].columns[1][0] == pkg.Candidates(*canonical(s, d))
