@@ -32,19 +32,15 @@ namespace gs {
 #ifndef GS_BK_UNROLL
 #define GS_BK_UNROLL 8
 #endif
+#ifndef GS_BK_PLAN_EARLY
+#define GS_BK_PLAN_EARLY 1   // speculative windows of integer policies: the work items planned inside k_sp_regions
+#endif
 constexpr uint32_t BK_ITEM = 1u << GS_BK_ITEM_LOG;
 
 namespace {
 
 // internal: the window does not fit the compact (32-bit offset) policy; rerun with the wide one
 constexpr gs_status GS_RETRY_WIDE = -100;
-
-struct BkMeta {   // offsets (u32 units) inside ctx->bk_meta
-  static constexpr size_t HIST = 0, DBASE = HIST + BK_MAXB, BSTART = DBASE + 512, BCOUNT = BSTART + BK_MAXB + 4,
-                          BITEMS = BCOUNT + BK_MAXB, BSLAB = BITEMS + BK_MAXB, MLIST = BSLAB + BK_MAXB,
-                          MAXIT = MLIST + BK_MAXB,   // the most items of one bucket (k_bk_merge_groups)
-                          TOTAL = MAXIT + 4;
-};
 
 struct BkGeom {
   int64_t base = 0;
@@ -137,6 +133,8 @@ void choose_passes(uint32_t nb, int* passes, int* w) {
 // records per accumulation work item: about GS_BK_ITEMS_PER_CU items per CU, at least 2^14 records
 #ifndef GS_BK_ITEMS_PER_CU
 #define GS_BK_ITEMS_PER_CU 3   // C2 (ms, one box): 4 items 1.712, 3 items 1.662 (fewer multi-item buckets: merge 0.066 -> 0.029), 2 items 1.685, 6 items 1.785
+                               // re-checked with the merges inside k_bk_accum (5 alternated runs, one box):
+                               // 3 items 1.347-1.435, 2 items 1.412-1.489, 4 items 1.443-1.482: 3 kept
 #endif
 uint32_t item_records(gs_ctx* c, uint64_t R) {
   const uint64_t per = R / (GS_BK_ITEMS_PER_CU * (uint64_t)std::max(1, c->n_cu));
@@ -152,13 +150,10 @@ gs_status ensure_cu(gs_ctx* c) {
   return GS_OK;
 }
 
-// k_bk_plan over meta[HIST] (bucket totals): bucket starts, work items, multi-item buckets
+// the plan's outputs, with the item and slab buffers sized for R records in nb buckets
 template <class P>
-// R: records (or, with cursor, the regions' total capacity) -- sizes the item and slab buffers.
-// cursor / counts_out: see BkPlanOut (speculative partition).
-gs_status launch_plan(gs_ctx* c, uint64_t R, uint32_t nb, int passes, int w, uint32_t item_recs,
-                      const uint32_t* cursor = nullptr, uint32_t* counts_out = nullptr,
-                      unsigned long long* occupied = nullptr) {
+gs_status plan_out(gs_ctx* c, uint64_t R, uint32_t nb, uint32_t item_recs, const uint32_t* cursor, uint32_t* counts_out,
+                   unsigned long long* occupied, BkPlanOut* po) {
   char* sm = c->small.as<char>();
   uint32_t* meta = c->bk_meta.as<uint32_t>();
   const uint64_t max_items = R / item_recs + nb + 1;
@@ -166,11 +161,25 @@ gs_status launch_plan(gs_ctx* c, uint64_t R, uint32_t nb, int passes, int w, uin
   GS_TRY(ensure(c, c->bk_items, max_items * sizeof(BkItem)));
   GS_TRY(ensure(c, c->bk_slabs, max_slabs * sizeof(typename P::Lds)));
   uint32_t* ns = (uint32_t*)(sm + SM_BK_N);
-  BkPlanOut po{meta + BkMeta::DBASE, meta + BkMeta::BSTART, meta + BkMeta::BCOUNT, meta + BkMeta::BITEMS,
-               meta + BkMeta::BSLAB, meta + BkMeta::MLIST, c->bk_items.as<BkItem>(), ns + 0, ns + 1,
-               cursor, counts_out, occupied, ns + 2, meta + BkMeta::MAXIT};
+  *po = BkPlanOut{meta + BkMeta::DBASE, meta + BkMeta::BSTART, meta + BkMeta::BCOUNT, meta + BkMeta::BITEMS,
+                  meta + BkMeta::BSLAB, meta + BkMeta::MLIST, c->bk_items.as<BkItem>(), ns + 0, ns + 1,
+                  cursor, counts_out, occupied, ns + 2, meta + BkMeta::MAXIT, meta + BkMeta::ARRIVE};
+  return GS_OK;
+}
+
+// k_bk_plan over meta[HIST] (bucket totals): bucket starts, work items, multi-item buckets
+template <class P>
+// R: records (or, with cursor, the regions' total capacity) -- sizes the item and slab buffers.
+// cursor / counts_out: see BkPlanOut (speculative partition).  expect_no_merge (speculative): the merge
+// launches are skipped, so a bucket that needs them is a miss.
+gs_status launch_plan(gs_ctx* c, uint64_t R, uint32_t nb, int passes, int w, uint32_t item_recs,
+                      const uint32_t* cursor = nullptr, uint32_t* counts_out = nullptr,
+                      unsigned long long* occupied = nullptr, bool expect_no_merge = false) {
+  uint32_t* meta = c->bk_meta.as<uint32_t>();
+  BkPlanOut po;
+  GS_TRY(plan_out<P>(c, R, nb, item_recs, cursor, counts_out, occupied, &po));
   hipLaunchKernelGGL(k_bk_plan, dim3(1), dim3(BK_PLAN_BLOCK), 0, c->stream, meta + BkMeta::HIST, nb, passes, w,
-                     item_recs, po);
+                     item_recs, bk_inline_k<P>(), expect_no_merge && occupied, po);
   return hip_check(c, hipGetLastError(), "k_bk_plan");
 }
 
@@ -179,10 +188,13 @@ gs_status launch_plan(gs_ctx* c, uint64_t R, uint32_t nb, int passes, int w, uin
 // read-back of the window's scalars (vertex range, outside-prediction count, U, items, escapes,
 // timeout) into host_small[0..7].  The caller waits (host_wait) and interprets them.  Records
 // pass_ev[ev0 + 1 .. ev0 + 3] after the three launches.  Every launch exits at once when the
-// histogram saw a key outside the predicted range (mm[2] != 0).
+// histogram saw a key outside the predicted range (mm[2] != 0).  skip_merge: the plan was told to expect no
+// bucket that needs the merge launches (launch_plan), so they are not launched.  counts_out: k_sp_regions
+// planned the items from the regions' capacities; the accumulate reports each bucket's count there and the
+// occupied bucket range in mm[0..1].
 template <class P, class Src>
 gs_status bucket_accumulate(gs_ctx* c, Src rs, uint64_t R, uint32_t nb, int64_t base, typename P::Out o, int ev0,
-                           const uint32_t* seg_cur = nullptr) {
+                           const uint32_t* seg_cur = nullptr, bool skip_merge = false, uint32_t* counts_out = nullptr) {
   char* sm = c->small.as<char>();
   uint32_t* meta = c->bk_meta.as<uint32_t>();
   uint32_t* ns = (uint32_t*)(sm + SM_BK_N);
@@ -194,20 +206,22 @@ gs_status bucket_accumulate(gs_ctx* c, Src rs, uint64_t R, uint32_t nb, int64_t 
   const bool dom = GS_DOM_ACCUM && ev0 == 2 && c->timing == GS_TIMING_DOMINANT;
   launch_dominant(c, dom ? c->pass_ev[7] : nullptr, dom ? c->pass_ev[ev0 + 1] : nullptr, k_bk_accum<P, Src, GS_BK_UNROLL>,
                   dim3(c->n_cu * GS_BK_ACC_PER_CU), dim3(BK_ACC_BLOCK), rs, (const BkItem*)c->bk_items.as<BkItem>(),
-                  (const uint32_t*)(ns + 0), (const uint32_t*)(meta + BkMeta::BSTART), ns + 2, slabs, st,
-                  meta + BkMeta::BCOUNT, mm, seg_cur);
+                  (const uint32_t*)(meta + BkMeta::BSTART), slabs, st, meta + BkMeta::BCOUNT,
+                  (unsigned long long*)(sm + SM_BK_MM), seg_cur, counts_out);
   GS_HIP(hipGetLastError());
   stage_event(c, c->pass_ev[ev0 + 1]);
   // blocks loop over the multi-item buckets (their number stays on the device)
   const unsigned mgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)nb, R / BK_ITEM + 1, 64}));
   const unsigned fgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)nb, R / BK_ITEM + 1, (uint64_t)c->n_cu}));
-  hipLaunchKernelGGL((k_bk_merge_groups<P>), dim3(2048), dim3(BK_MS_BLOCK), 0, c->stream, meta + BkMeta::MLIST, ns + 1,
-                     meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, slabs, mm, (const uint32_t*)(meta + BkMeta::MAXIT));
-  hipLaunchKernelGGL((k_bk_merge_slices<P>), dim3(mgrid, BK_MS_SLICES), dim3(BK_MS_BLOCK), 0, c->stream,
-                     meta + BkMeta::MLIST, ns + 1, meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, slabs, mm);
-  hipLaunchKernelGGL((k_bk_merge<P>), dim3(fgrid), dim3(BK_ACC_BLOCK), 0, c->stream, meta + BkMeta::MLIST, ns + 1,
-                     meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, meta + BkMeta::BSTART, slabs, st,
-                     meta + BkMeta::BCOUNT, mm);
+  if (!skip_merge) {
+    hipLaunchKernelGGL((k_bk_merge_groups<P>), dim3(2048), dim3(BK_MS_BLOCK), 0, c->stream, meta + BkMeta::MLIST, ns + 1,
+                       meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, slabs, mm, (const uint32_t*)(meta + BkMeta::MAXIT));
+    hipLaunchKernelGGL((k_bk_merge_slices<P>), dim3(mgrid, BK_MS_SLICES), dim3(BK_MS_BLOCK), 0, c->stream,
+                       meta + BkMeta::MLIST, ns + 1, meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, slabs, mm);
+    hipLaunchKernelGGL((k_bk_merge<P>), dim3(fgrid), dim3(BK_ACC_BLOCK), 0, c->stream, meta + BkMeta::MLIST, ns + 1,
+                       meta + BkMeta::BITEMS, meta + BkMeta::BSLAB, meta + BkMeta::BSTART, slabs, st,
+                       meta + BkMeta::BCOUNT, mm);
+  }
   GS_HIP(hipGetLastError());
   stage_event(c, c->pass_ev[ev0 + 2]);
   if (c->oe.nparts) {   // gs_window_reduce_dist: the exchange's rows instead of the ascending output
@@ -423,8 +437,9 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
         continue;
       }
       if (spec && attempt == 0) {
-        // regions from the previous window's counts -> the scatter reserves runs with atomics ->
-        // items from the cursors (the counts the next window predicts from) -> accumulate
+        // regions from the previous window's counts (integer policies: and the items, from the regions'
+        // capacities) -> the scatter reserves runs with atomics -> (other policies: items from the cursors)
+        // -> accumulate, which also reports the counts the next window predicts from
         // each XCD slot's share of the records (k_sp_scatter_pack: slot x owns full tiles [x·per, (x+1)·per),
         // the partial last tile runs in slot 0)
         SpSlots slots{};
@@ -442,9 +457,18 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
           }
           slots.pre[SP_NSEG] = (uint32_t)acc;   // == R
         }
+        // the previous window had no bucket for the merge launches: none are launched, and the plan counts one
+        // that turns up as a miss
+        const bool no_merge = bk_inline_k<P>() > 1 && sp.n_merge == 0;
+        // integer policies: the items planned from the regions' capacities inside k_sp_regions, no launch
+        // between the scatter and the accumulate (float sums keep k_bk_plan over the cursors: their items, and
+        // with them the order of their merges, stay what they were)
+        constexpr bool PLAN_EARLY = GS_BK_PLAN_EARLY && bk_inline_k<P>() > 1;
+        BkPlanOut po{};
+        if (PLAN_EARLY) GS_TRY(plan_out<P>(c, cap, nb, item_recs, nullptr, nullptr, nullptr, &po));
         hipLaunchKernelGGL(k_sp_regions, dim3(1), dim3(BK_PLAN_BLOCK), 0, c->stream, (const uint32_t*)sp.tot.as<uint32_t>(),
                            nb, sp.R, R, meta + BkMeta::BSTART, c->sp_cur.as<uint32_t>(), slots, mm,
-                           (unsigned long long*)(sm + SM_BK_ESC));
+                           (unsigned long long*)(sm + SM_BK_ESC), item_recs, bk_inline_k<P>(), no_merge, po);
         if constexpr (P::REL) GS_HIP(hipMemsetAsync(rel_bad, 0, 4, c->stream));
         stage_event(c, c->ev[1]);
         stage_event(c, c->pass_ev[0]);
@@ -478,10 +502,13 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
         GS_HIP(hipGetLastError());
         stage_event(c, c->pass_ev[2]);
         stage_event(c, c->ev[2]);
-        GS_TRY(launch_plan<P>(c, cap, nb, 0, 0, item_recs, cur, sp.tot.as<uint32_t>(), mm));
+        if (!PLAN_EARLY) GS_TRY(launch_plan<P>(c, cap, nb, 0, 0, item_recs, cur, sp.tot.as<uint32_t>(), mm, no_merge));
         part = true;
-        if (pack) GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{c->keysB.as<uint32_t>(), vpart}, cap, nb, base, o, 2, cur)));
-        else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, cap, nb, base, o, 2, cur)));
+        uint32_t* counts = PLAN_EARLY ? sp.tot.as<uint32_t>() : nullptr;
+        if (pack)
+          GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{c->keysB.as<uint32_t>(), vpart}, cap, nb, base, o, 2, cur, no_merge,
+                                       counts)));
+        else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, cap, nb, base, o, 2, cur, no_merge, counts)));
         if (defer) return GS_PENDING_LOCAL;
         GS_TRY(bucket_wait(c));
         if (!c->host_small[2]) {   // hit: every key in the range; the plan reported the occupied buckets
@@ -598,6 +625,10 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
       sp.S = S;
       sp.dir = DIR;
       sp.R = R;
+      // the plan's n_multi (SM_BK_N's second word).  After a histogram window the next window still launches the
+      // merges: its items follow the regions' capacities, which can put a bucket one item over the limit that
+      // this window's counts kept under it -- the speculative window's own plan then says what the one after needs
+      sp.n_merge = std::max<uint32_t>((uint32_t)(c->host_small[4] >> 32), spec ? 0u : 1u);
     }
   }
   return GS_OK;

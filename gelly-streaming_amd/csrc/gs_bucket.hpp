@@ -15,7 +15,9 @@
 //   k_bk_accum   one persistent workgroup per CU takes items (bucket, record range), adds every
 //                record into LDS accumulators with LDS atomics (ds_add/min/max), then writes the
 //                bucket's vertices in ascending order (wave ballot compaction) to a staging area;
-//                buckets larger than one item leave LDS slabs that k_bk_merge combines;
+//                a bucket of 2 .. GS_BK_INLINE_K items (integer accumulators) is merged in LDS by the
+//                item that arrives last; larger buckets and float sums leave LDS slabs that
+//                k_bk_merge_groups / _slices / k_bk_merge combine;
 //   k_bk_emit    staging -> (vertex, value) outputs, vertices ascending (the sort path's order).
 // Integer results are bit-exact (wrapping adds, min / max); f64 / f32 sums are summed in f64 in
 // LDS-atomic order, within the API's 1e-5 relative tolerance.  Float MIN / MAX keep the sort path
@@ -24,6 +26,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "gs_internal.hpp"
 #include "gs_radix.hpp"
 #include "gs_rbk.hpp"
 
@@ -41,9 +44,21 @@ constexpr int BK_INFO_BLOCK = 512;
 #endif
 #ifndef GS_BK_PREFETCH
 #define GS_BK_PREFETCH 0   // k_bk_accum: the next item's first loads issued before the current item's finalize
-                           // (A/B, round 6: accumulate 0.2560 -> 0.2728 ms on C2 -- the barrier after the finalize
-                           // waits for them, so they hide nothing and hold VGPRs: off)
+                           // (A/B, round 6: accumulate 0.2560 -> 0.2728 ms on C2.  Not the barriers: every
+                           // s_barrier of k_bk_accum waits on lgkmcnt(0) only.  The prefetched registers are
+                           // loop-carried, and the compiler drains them with s_waitcnt vmcnt(0) before the
+                           // finalize's first pass, so they hide nothing and hold VGPRs: off)
 #endif
+#ifndef GS_BK_INLINE_K
+#define GS_BK_INLINE_K 4   // k_bk_accum: a bucket of 2 .. K items is merged in LDS by its last item (integer
+                           // accumulators only); larger buckets keep k_bk_merge_groups / _slices / k_bk_merge
+#endif
+// the buckets of 2 .. bk_inline_k<P>() items need no merge launch (0: every multi-item bucket does).  Float sums
+// keep the launched merges: their merge order is fixed there, an arrival order would not be
+template <class P>
+__host__ __device__ constexpr uint32_t bk_inline_k() {
+  return std::is_integral_v<typename P::A> && GS_BK_INLINE_K > 1 ? (uint32_t)GS_BK_INLINE_K : 0u;
+}
 #ifndef GS_BK_FUSED_RESET
 #define GS_BK_FUSED_RESET 1   // k_bk_accum: each wave resets its own finalized entries (no block-wide init pass)
 #endif
@@ -64,13 +79,23 @@ struct BkStage {
   int64_t* b;    // second accumulator (degree fold: max neighbour)
 };
 
+// offsets (u32 units) inside ctx->bk_meta.  k_bk_accum takes the bucket_count pointer and reaches b_items, b_slab
+// and the arrival counters from it (fewer kernel arguments: each pointer is an SGPR pair held across the stream)
+struct BkMeta {
+  static constexpr size_t HIST = 0, DBASE = HIST + BK_MAXB, BSTART = DBASE + 512, BCOUNT = BSTART + BK_MAXB + 4,
+                          BITEMS = BCOUNT + BK_MAXB, BSLAB = BITEMS + BK_MAXB, MLIST = BSLAB + BK_MAXB,
+                          MAXIT = MLIST + BK_MAXB,   // the most items of one bucket (k_bk_merge_groups)
+                          ARRIVE = MAXIT + 4,        // per-bucket arrival counters (k_bk_accum's inline merge)
+                          TOTAL = ARRIVE + BK_MAXB;
+};
+
 struct BkPlanOut {
   uint32_t* digit_base;    // [2][256]
   uint32_t* bucket_start;  // [NB + 1]
   uint32_t* bucket_count;  // [NB]   outputs per bucket (written by finalize)
   uint32_t* b_items;       // [NB]
   uint32_t* b_slab;        // [NB]   first slab of a multi-item bucket
-  uint32_t* mlist;         // [NB]   multi-item buckets
+  uint32_t* mlist;         // [NB]   the multi-item buckets the merge launches combine (more than inline_k items)
   BkItem* items;
   uint32_t* n_items;       // device scalars
   uint32_t* n_multi;
@@ -82,6 +107,7 @@ struct BkPlanOut {
   unsigned long long* occupied = nullptr;   // speculative: [0] lowest, [1] highest bucket with records
   uint32_t* claim = nullptr;                // k_bk_accum's item counter, zeroed here
   uint32_t* max_items = nullptr;            // the most items of one bucket (k_bk_merge_groups skips when <= 16)
+  uint32_t* arrive = nullptr;               // [NB]   k_bk_accum's per-bucket arrival counter, zeroed here
 };
 
 // speculative partition: a bucket's region is split into SP_NSEG segments, one per XCD slot, each with
@@ -570,23 +596,112 @@ __device__ __forceinline__ uint32_t bk_block_scan(uint32_t x, uint32_t* s_w, uin
   return off + inc - x;
 }
 
-// ---- k_bk_plan: digit bases of the partition passes, bucket starts, work items (one block) -------
 #ifndef GS_BK_LPT
 #define GS_BK_LPT 1
 #endif
 constexpr int BK_LPT_CLASSES = 64;
+// the work items of buckets 2 tid and 2 tid + 1 (c0, c1 records; one block of BK_PLAN_BLOCK threads): a bucket
+// of cnt records is split into ceil(cnt / item_recs) items; multi-item buckets get consecutive slabs.  A bucket
+// of 2 .. inline_k items is merged inside k_bk_accum; n_multi / mlist count the others, which the merge
+// launches combine.  Returns n_multi.  Shared by k_bk_plan (the counts) and k_sp_regions (the regions' capacities).
+__device__ __forceinline__ uint32_t bk_plan_items(uint32_t c0, uint32_t c1, uint32_t nb, uint32_t item_recs,
+                                                  uint32_t inline_k, const BkPlanOut& o, uint32_t* s_w) {
+  __shared__ uint32_t s_maxit;
+  const int tid = threadIdx.x;
+  const uint32_t b0 = 2 * tid, b1 = 2 * tid + 1;
+  if (tid == 0) s_maxit = 0;
+  auto nitems = [&](uint32_t c) { return c == 0 ? 0u : (c + item_recs - 1) / item_recs; };
+  const uint32_t i0 = nitems(c0), i1 = nitems(c1);
+  const uint32_t m0 = i0 > 1 ? i0 : 0u, m1 = i1 > 1 ? i1 : 0u;
+  const uint32_t lk = max(1u, inline_k);   // more items than this: a launched merge
+  const uint32_t g0 = i0 > lk ? 1u : 0u, g1 = i1 > lk ? 1u : 0u;
+  uint32_t n_items, n_slabs, n_multi;
+  const uint32_t first0 = bk_block_scan(i0 + i1, s_w, n_items);
+  const uint32_t slab0 = bk_block_scan(m0 + m1, s_w, n_slabs);
+  const uint32_t mb0 = bk_block_scan(g0 + g1, s_w, n_multi);
+#if GS_BK_LPT
+  // claim order: largest items first (k_bk_accum's workgroups take items from a counter, so the small
+  // ones fill the gaps at the end instead of a large one starting last): a counting sort over
+  // BK_LPT_CLASSES size classes, descending; the order within a class is free
+  __shared__ uint32_t s_cls[BK_LPT_CLASSES];
+  for (int i = tid; i < BK_LPT_CLASSES; i += BK_PLAN_BLOCK) s_cls[i] = 0;
+  __syncthreads();
+  auto size_class = [&](uint32_t n) -> uint32_t {   // larger items -> smaller class
+    return BK_LPT_CLASSES - 1 - min<uint32_t>(BK_LPT_CLASSES - 1, (uint32_t)((uint64_t)n * BK_LPT_CLASSES / (item_recs + 1)));
+  };
+  // a bucket's items are ni - 1 full ones and its last piece: one atomic for each group (a hub bucket of
+  // a Zipf stream has hundreds of items; one atomic per item serialised the plan's thread)
+  // (the last piece of a bucket merged inside k_bk_accum is claimed with the bucket's full items: claimed in its
+  // own, small size class it would arrive at the end of the kernel and its merge would be the kernel's tail)
+  auto count_items = [&](uint32_t b, uint32_t c, uint32_t ni) {
+    if (b >= nb || !ni) return;
+    const bool together = ni > 1 && ni <= inline_k;
+    if (ni > 1) atomicAdd(&s_cls[size_class(item_recs)], together ? ni : ni - 1);
+    if (!together) atomicAdd(&s_cls[size_class(c - (ni - 1) * item_recs)], 1u);
+  };
+  count_items(b0, c0, i0);
+  count_items(b1, c1, i1);
+  __syncthreads();
+  static_assert(BK_LPT_CLASSES == WAVE, "one wave scans the classes");
+  if (tid < WAVE) {
+    const uint32_t x = s_cls[tid];
+    s_cls[tid] = wave_inclusive_sum(x) - x;
+  }
+  __syncthreads();
+#endif
+  auto emit_bucket = [&](uint32_t b, uint32_t c, uint32_t ni, uint32_t first, uint32_t slab, uint32_t mb) {
+    if (b >= nb) return;
+    o.bucket_count[b] = 0;
+    o.b_items[b] = ni;
+    o.b_slab[b] = slab;
+    if (o.arrive) o.arrive[b] = 0;
+    if (ni > lk) o.mlist[mb] = b;
+    if (!ni) return;
+#if GS_BK_LPT
+    const bool together = ni > 1 && ni <= inline_k;
+    const uint32_t fpos = ni > 1 ? atomicAdd(&s_cls[size_class(item_recs)], together ? ni : ni - 1) : 0u;   // the full items
+    const uint32_t lpos = together ? fpos + ni - 1 : atomicAdd(&s_cls[size_class(c - (ni - 1) * item_recs)], 1u);   // the last piece
+#endif
+    for (uint32_t k = 0; k < ni; ++k) {
+      BkItem it;
+      it.bucket = b;
+      it.begin = k * item_recs;   // relative; made absolute below
+      it.end = min(c, (k + 1) * item_recs);
+      it.slab = ni > 1 ? slab + k : ~0u;
+#if GS_BK_LPT
+      o.items[k + 1 < ni ? fpos + k : lpos] = it;
+#else
+      o.items[first + k] = it;
+#endif
+    }
+  };
+  emit_bucket(b0, c0, i0, first0, slab0, mb0);
+  emit_bucket(b1, c1, i1, first0 + i0, slab0 + m0, mb0 + g0);
+  if (o.max_items) {   // (s_maxit: zeroed before the item scans' barriers)
+    if (i0 > 1 || i1 > 1) atomicMax(&s_maxit, max(i0, i1));
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (o.max_items) *o.max_items = s_maxit;
+    *o.n_items = n_items;
+    *o.n_multi = n_multi;
+  }
+  return n_multi;
+}
+
+// ---- k_bk_plan: digit bases of the partition passes, bucket starts, work items (one block) -------
 // pass p ranks digit (bucket >> (p * w)) & (2^w - 1); bucket b's records end up at
-// [bucket_start[b], bucket_start[b + 1]).  Items: a bucket of cnt records is split into
-// ceil(cnt / item_recs) items; multi-item buckets get consecutive slabs.
+// [bucket_start[b], bucket_start[b + 1]).  Items: bk_plan_items.  The host skips the merge launches when the
+// previous window had no bucket for them (expect_no_merge): if this window has one after all, the plan raises
+// the miss count and the window reruns through the histogram path.
 static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_bk_plan(const uint32_t* __restrict__ hist, uint32_t nb,
                                                                   int passes, int w, uint32_t item_recs,
+                                                                  uint32_t inline_k, bool expect_no_merge,
                                                                   BkPlanOut o) {
   __shared__ uint32_t s_dh[2][256];
   __shared__ uint32_t s_w[BK_PLAN_BLOCK / WAVE];
-  __shared__ uint32_t s_maxit;
   const int tid = threadIdx.x;
   for (int i = tid; i < 2 * 256; i += BK_PLAN_BLOCK) (&s_dh[0][0])[i] = 0;
-  if (tid == 0) s_maxit = 0;
   if (tid == 0 && o.claim) *o.claim = 0;
   __syncthreads();
   // two buckets per thread (BK_MAXB = 2 * BK_PLAN_BLOCK)
@@ -641,76 +756,8 @@ static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_bk_plan(const uint32_t
       run += s_dh[tid][d];
     }
   }
-  // items
-  auto nitems = [&](uint32_t c) { return c == 0 ? 0u : (c + item_recs - 1) / item_recs; };
-  const uint32_t i0 = nitems(c0), i1 = nitems(c1);
-  const uint32_t m0 = i0 > 1 ? i0 : 0u, m1 = i1 > 1 ? i1 : 0u;
-  uint32_t n_items, n_slabs, n_multi;
-  const uint32_t first0 = bk_block_scan(i0 + i1, s_w, n_items);
-  const uint32_t slab0 = bk_block_scan(m0 + m1, s_w, n_slabs);
-  const uint32_t mb0 = bk_block_scan((m0 ? 1u : 0u) + (m1 ? 1u : 0u), s_w, n_multi);
-#if GS_BK_LPT
-  // claim order: largest items first (k_bk_accum's workgroups take items from a counter, so the small
-  // ones fill the gaps at the end instead of a large one starting last): a counting sort over
-  // BK_LPT_CLASSES size classes, descending; the order within a class is free
-  __shared__ uint32_t s_cls[BK_LPT_CLASSES];
-  for (int i = tid; i < BK_LPT_CLASSES; i += BK_PLAN_BLOCK) s_cls[i] = 0;
-  __syncthreads();
-  auto size_class = [&](uint32_t n) -> uint32_t {   // larger items -> smaller class
-    return BK_LPT_CLASSES - 1 - min<uint32_t>(BK_LPT_CLASSES - 1, (uint32_t)((uint64_t)n * BK_LPT_CLASSES / (item_recs + 1)));
-  };
-  // a bucket's items are ni - 1 full ones and its last piece: one atomic for each group (a hub bucket of
-  // a Zipf stream has hundreds of items; one atomic per item serialised the plan's thread)
-  auto count_items = [&](uint32_t b, uint32_t c, uint32_t ni) {
-    if (b >= nb || !ni) return;
-    if (ni > 1) atomicAdd(&s_cls[size_class(item_recs)], ni - 1);
-    atomicAdd(&s_cls[size_class(c - (ni - 1) * item_recs)], 1u);
-  };
-  count_items(b0, c0, i0);
-  count_items(b1, c1, i1);
-  __syncthreads();
-  static_assert(BK_LPT_CLASSES == WAVE, "one wave scans the classes");
-  if (tid < WAVE) {
-    const uint32_t x = s_cls[tid];
-    s_cls[tid] = wave_inclusive_sum(x) - x;
-  }
-  __syncthreads();
-#endif
-  auto emit_bucket = [&](uint32_t b, uint32_t c, uint32_t ni, uint32_t first, uint32_t slab, uint32_t mb) {
-    if (b >= nb) return;
-    o.bucket_count[b] = 0;
-    o.b_items[b] = ni;
-    o.b_slab[b] = slab;
-    if (ni > 1) o.mlist[mb] = b;
-    if (!ni) return;
-#if GS_BK_LPT
-    const uint32_t fpos = ni > 1 ? atomicAdd(&s_cls[size_class(item_recs)], ni - 1) : 0u;   // the full items
-    const uint32_t lpos = atomicAdd(&s_cls[size_class(c - (ni - 1) * item_recs)], 1u);     // the last piece
-#endif
-    for (uint32_t k = 0; k < ni; ++k) {
-      BkItem it;
-      it.bucket = b;
-      it.begin = k * item_recs;   // relative; made absolute below
-      it.end = min(c, (k + 1) * item_recs);
-      it.slab = ni > 1 ? slab + k : ~0u;
-#if GS_BK_LPT
-      o.items[k + 1 < ni ? fpos + k : lpos] = it;
-#else
-      o.items[first + k] = it;
-#endif
-    }
-  };
-  emit_bucket(b0, c0, i0, first0, slab0, mb0);
-  emit_bucket(b1, c1, i1, first0 + i0, slab0 + m0, mb0 + (m0 ? 1u : 0u));
-  if (o.max_items) {   // (s_maxit complete after the item scans' barriers)
-    if (i0 > 1 || i1 > 1) atomicMax(&s_maxit, max(i0, i1));
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (o.max_items) *o.max_items = s_maxit;
-    *o.n_items = n_items;
-    *o.n_multi = n_multi;
-  }
+  const uint32_t n_multi = bk_plan_items(c0, c1, nb, item_recs, inline_k, o, s_w);
+  if (tid == 0 && expect_no_merge && n_multi) atomicAdd(&o.occupied[2], 1ull);   // (speculative: occupied = mm)
 }
 
 // ---- direct partition: the whole bucket index in ONE scatter pass ----------------------------------
@@ -1187,13 +1234,22 @@ void k_dp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
 // miss).  Record order inside a bucket follows the atomics: integer SUM / MIN / MAX only (exact in
 // any order).
 
-// bucket regions from the previous window's counts (one block): starts, cursors, mm reset
+// bucket regions from the previous window's counts (one block): starts, cursors, mm reset.
+// With plan.items (integer policies) also the accumulate's work items, planned from the regions' capacities
+// instead of the cursors the scatter leaves: a bucket of capacity cap gets ceil(cap / item_recs) items, the
+// last one ending at cap, and k_bk_accum clamps every item to the records that arrived (a run that does not
+// fit its segment is a miss anyway).  Every bucket below nb has a capacity of at least SP_PAD, so at least one
+// item.  No launch then sits between the scatter and the accumulate; what needs the cursors -- the counts the
+// next window's regions are sized from and the occupied bucket range in mm[0..1] -- is written by the item
+// of each bucket that starts at record 0 (k_bk_accum's prepare, which loads the cursors anyway).
 static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_sp_regions(const uint32_t* __restrict__ prev, uint32_t nb,
                                                                      uint64_t r_prev, uint64_t r_now,
                                                                      uint32_t* __restrict__ bucket_start,
                                                                      uint32_t* __restrict__ cursor, SpSlots slots,
                                                                      unsigned long long* __restrict__ mm,
-                                                                     unsigned long long* __restrict__ n_esc) {
+                                                                     unsigned long long* __restrict__ n_esc,
+                                                                     uint32_t item_recs, uint32_t inline_k,
+                                                                     bool expect_no_merge, BkPlanOut plan) {
   __shared__ uint32_t s_w[BK_PLAN_BLOCK / WAVE];
   __shared__ uint32_t s_frac[SP_NSEG + 1];
   const int tid = threadIdx.x;
@@ -1231,8 +1287,19 @@ static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_sp_regions(const uint3
     l1 = h1;
   }
   if (tid == 0) bucket_start[nb] = total;
-  if (tid < 4) mm[tid] = 0;
   if (tid == 4) *n_esc = 0;
+  if (!plan.items) {
+    if (tid < 4) mm[tid] = 0;
+    return;
+  }
+  if (tid == 0) *plan.claim = 0;
+  const uint32_t n_multi = bk_plan_items(c0, c1, nb, item_recs, inline_k, plan, s_w);
+  if (tid == 0) {
+    mm[0] = ~0u;   // k_bk_accum: atomicMin / atomicMax of the occupied buckets (no bucket: k_bk_plan's ~0u)
+    mm[1] = 0;
+    mm[2] = expect_no_merge && n_multi ? 1 : 0;   // a bucket for the merge launches the host skips: a miss
+    mm[3] = 0;
+  }
 }
 
 // the host's bound on k_sp_regions' total (sum of t <= r_now)
@@ -1783,6 +1850,24 @@ __device__ __forceinline__ void bk_finalize(typename P::Lds& s, uint32_t bucket,
   if (tid == 0) bucket_count[bucket] = tot;
 }
 
+// k_bk_accum's inline merge: slabs first[0 .. ni) of a bucket, but the caller's own (`mine`) and those of items
+// without records (bits of `empties`), combined into the caller's live table *s, element by element as
+// k_bk_merge_slices does, one slab after the other.  Not inlined: it runs once per merged bucket, and inlined its
+// registers added spills to the record stream of the instantiations that sit at the 128-VGPR cap (4-byte
+// accumulators); the kernels' register and scratch figures are the parent's this way.
+template <class P>
+__device__ __attribute__((noinline)) void bk_merge_slabs(typename P::Lds* s, const typename P::Lds* first, uint32_t ni,
+                                                         uint32_t mine, uint32_t empties) {
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t k = 0; k < ni; ++k) {
+    if (k == mine || ((empties >> k) & 1u)) continue;   // (block-uniform)
+    const typename P::Lds* g = first + k;
+#pragma unroll 4
+    for (uint32_t i = tid; i < P::W; i += BK_ACC_BLOCK) P::merge_el(s, g, i);
+    for (uint32_t w = tid; w < P::PWORDS; w += BK_ACC_BLOCK) P::merge_pw(s, g, w);
+  }
+}
+
 #ifdef GS_BK_TRACE
 constexpr uint32_t BK_TRACE_MAX = 16384;
 __device__ uint64_t g_bk_trace[BK_TRACE_MAX][4];
@@ -1795,15 +1880,30 @@ __device__ uint64_t g_bk_trace[BK_TRACE_MAX][4];
 // head / tail records, one record after another) behind two barriers, with no stream load in flight on the CU.
 template <class P, class Src, int UNROLL>
 __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem* __restrict__ items,
-                                                           const uint32_t* __restrict__ n_items_p,
                                                            const uint32_t* __restrict__ bucket_start,
-                                                           uint32_t* __restrict__ ctr,
                                                            typename P::Lds* __restrict__ slabs, BkStage st,
                                                            uint32_t* __restrict__ bucket_count,
-                                                           const unsigned long long* __restrict__ mm,
-                                                           const uint32_t* __restrict__ seg_cur) {
+                                                           unsigned long long* __restrict__ mm,
+                                                           const uint32_t* __restrict__ seg_cur,
+                                                           uint32_t* __restrict__ counts_out) {
+  // the plan's scalars sit behind mm (SM_BK_N = SM_BK_MM + 32: items, multi buckets, the claim counter), the
+  // per-bucket item counts, first slabs and arrival counters behind bucket_count (BkMeta)
+  static_assert(SM_BK_N == SM_BK_MM + 4 * sizeof(unsigned long long), "ns = mm + 4");
+  static_assert(BkMeta::BCOUNT < BkMeta::BITEMS && BkMeta::BITEMS < BkMeta::BSLAB && BkMeta::BSLAB < BkMeta::ARRIVE &&
+                    BkMeta::ARRIVE + BK_MAXB <= BkMeta::TOTAL,
+                "b_items, b_slab and the arrival counters follow bucket_count inside bk_meta");
+  uint32_t* const ns = reinterpret_cast<uint32_t*>(mm + 4);   // [0] items, [1] multi buckets, [2] the claim counter
+  uint32_t* const ctr = ns + 2;
+  const uint32_t* const b_items = bucket_count + (BkMeta::BITEMS - BkMeta::BCOUNT);
+  const uint32_t* const b_slab = bucket_count + (BkMeta::BSLAB - BkMeta::BCOUNT);
+  uint32_t* const arrive = bucket_count + (BkMeta::ARRIVE - BkMeta::BCOUNT);
   __shared__ typename P::Lds s;
   __shared__ uint32_t s_item[2], s_b0[2];   // two slots: the current item and the one wave 0 stages
+  __shared__ uint32_t s_ni[2], s_f[2];      // the item's bucket: its items and its first slab (multi-item buckets)
+  __shared__ uint32_t s_last;               // this item is the last of its bucket to arrive (bit 31) | empty items
+  __shared__ uint32_t s_nrec[2], s_tot[2];  // the item's records; (counts_out) its bucket's
+  constexpr uint32_t IK = bk_inline_k<P>();
+  static_assert(IK <= 16, "the arrival counter: 8 bits of tickets, a bit per empty item above them");
   __shared__ BkItem s_m[2];
   __shared__ uint32_t s_wc[BK_NW];
   __shared__ uint32_t s_pre4[2][SP_NSEG + 1], s_qb[2][SP_NSEG];   // packed records: the item's pieces as one stream
@@ -1811,7 +1911,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
   constexpr bool PACKED = is_pack_src<Src>::value;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   if (mm[2]) return;   // keys outside the predicted range: the window is rerun
-  const uint32_t n_items = *n_items_p;
+  const uint32_t n_items = ns[0];
   // packed records: one record into LDS (the value from `wide` when escaped)
   auto add1 = [&](const auto& sr, uint32_t q, uint32_t x) {
     const uint32_t v16 = x >> 16;
@@ -1837,17 +1937,43 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
       s_m[b] = m;
       s_b0[b] = b0;
     }
-    if constexpr (PACKED) {
-      if (seg_cur) {
-        // the item's pieces of the bucket's SP_NSEG segments, in segment order, as ONE stream of 16-byte
-        // groups (a loop per segment drained and refilled the loads in flight at each segment boundary):
-        // lane x < SP_NSEG takes segment x's piece [p0, p1) and publishes its groups' place in the stream
-        const bool on = lane < (int)SP_NSEG;
-        const uint32_t x = on ? (uint32_t)lane : 0u;
-        const uint32_t sg = sp_lo(seg_cur, x, m.bucket);
-        const uint32_t nx = on ? min(seg_cur[x * BK_MAXB + m.bucket], sp_hi(seg_cur, x, m.bucket)) - sg : 0u;
-        const uint32_t at = wave_inclusive_sum(nx) - nx;   // records of the bucket in the segments before x
-        const uint32_t lo = max(m.begin, at), hi = min(m.end, at + nx);
+    if constexpr (IK > 1) {
+      if (m.slab != ~0u) {   // (wave-uniform)
+        const uint32_t ni = b_items[m.bucket], f = b_slab[m.bucket];
+        if (lane == 0) {
+          s_ni[b] = ni;
+          s_f[b] = f;
+        }
+      }
+    }
+    // The bucket's records lie in its SP_NSEG segments (speculative partition): lane x < SP_NSEG takes segment x,
+    // [lo, hi) is the part of the item's [m.begin, m.end) in it.
+    // counts_out (k_sp_regions planned the items from the regions' capacities): the item holds the records of
+    // [m.begin, m.end) that arrived, possibly none; the item at record 0 reports what the plan used to take from
+    // the cursors -- the bucket's count (the next window's regions) and, if it has records, the occupied range
+    uint32_t nrec = m.end - m.begin, tot = 1;
+    if (seg_cur && (PACKED || counts_out)) {
+      const bool on = lane < (int)SP_NSEG;
+      const uint32_t x = on ? (uint32_t)lane : 0u;
+      const uint32_t sg = sp_lo(seg_cur, x, m.bucket);
+      const uint32_t nx = on ? min(seg_cur[x * BK_MAXB + m.bucket], sp_hi(seg_cur, x, m.bucket)) - sg : 0u;
+      const uint32_t inc = wave_inclusive_sum(nx), at = inc - nx;   // at: records of the bucket in the segments before x
+      const uint32_t lo = max(m.begin, at), hi = min(m.end, at + nx);
+      if (counts_out) {
+        tot = __shfl(inc, WAVE - 1, WAVE);
+        nrec = __shfl(wave_inclusive_sum(on && lo < hi ? hi - lo : 0u), WAVE - 1, WAVE);
+        if (lane == 0 && m.begin == 0) {
+          counts_out[m.bucket] = tot;
+          if (tot) {
+            atomicMin(&mm[0], (unsigned long long)m.bucket);
+            atomicMax(&mm[1], (unsigned long long)m.bucket);
+          }
+        }
+      }
+      if constexpr (PACKED) {
+        // the item's pieces, in segment order, as ONE stream of 16-byte groups (a loop per segment drained and
+        // refilled the loads in flight at each segment boundary): lane x takes segment x's piece [p0, p1) and
+        // publishes its groups' place in the stream
         uint32_t p0 = 0, p1 = 0;
         if (on && lo < hi) {
           p0 = sg + (lo - at);
@@ -1871,6 +1997,10 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
           hx = src.rec[q];
         }
       }
+    }
+    if (lane == 0) {
+      s_nrec[b] = nrec;
+      s_tot[b] = tot;
     }
   };
   if (tid < WAVE) prepare(0);
@@ -2086,14 +2216,80 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
     }
 #endif
     bool reset = false;
+    const uint32_t nrec = s_nrec[sl];   // (read here: not live across the stream)
     if (m.slab == ~0u) {
-      bk_finalize<P, GS_BK_FUSED_RESET != 0>(s, m.bucket, b0, st, bucket_count, s_wc);
-      reset = GS_BK_FUSED_RESET != 0;
+      // (an item without records: its bucket is empty, its count stays the plan's 0 and the table is untouched)
+      if (nrec) bk_finalize<P, GS_BK_FUSED_RESET != 0>(s, m.bucket, b0, st, bucket_count, s_wc);
+      reset = !nrec || GS_BK_FUSED_RESET != 0;
     } else {
-      // dump the LDS accumulators (k_bk_merge, a later launch, combines the bucket's slabs)
-      const uint4* ls = reinterpret_cast<const uint4*>(&s);
-      uint4* gs = reinterpret_cast<uint4*>(slabs + m.slab);
-      for (uint32_t i = tid; i < sizeof(typename P::Lds) / 16; i += BK_ACC_BLOCK) gs[i] = ls[i];
+      // A bucket of 2 .. IK items is merged here: every item but the last to arrive dumps its table and then
+      // takes a ticket on the bucket's arrival counter; the last adds the other slabs into its live table and
+      // finalizes as for a single-item bucket.  No workgroup waits for another.  An item that finds the
+      // counter at ni - 1 before dumping is the last and skips the dump; one that learns it only from its
+      // ticket has dumped for nothing, which is harmless.  The dumping and the merging workgroup usually sit
+      // on different XCDs: the dump is released at agent scope before the ticket (every wave's stores
+      // complete, then one write-back of the L2), and the merger acquires at agent scope before its loads.
+      // An item without records (capacity plan) has nothing to dump: it sets its bit above the tickets instead and
+      // the merger skips its slab; the items of a bucket without any record skip all of it (the count stays 0).
+      bool last = false, merged = false, idle = false;   // idle: an item without records that need not dump
+      uint32_t ni = 0, f = 0, mine = 0, empties = 0;
+      auto arrived = [&](uint32_t v) { return (v & 0xFFu) == ni - 1 ? 0x80000000u | (v >> 8) : 0u; };
+      if constexpr (IK > 1) {
+        ni = s_ni[sl];
+        f = s_f[sl];
+        mine = m.slab - f;
+        merged = ni <= IK && s_tot[sl] != 0;   // (block-uniform)
+        if (merged) {
+          if (tid == 0)
+            s_last = arrived(__hip_atomic_load(&arrive[m.bucket], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+          __syncthreads();
+          last = s_last != 0;
+          empties = s_last & 0xFFFFu;
+        }
+        idle = ni <= IK && !nrec;
+        if (idle) reset = true;   // neither records nor, unless it is the last, a merge: the table stays clean
+      }
+      if (!last && !idle) {
+        // dump the LDS accumulators (a later item of the bucket, or k_bk_merge in a later launch, combines them)
+        const uint4* ls = reinterpret_cast<const uint4*>(&s);
+        uint4* gs = reinterpret_cast<uint4*>(slabs + m.slab);
+        for (uint32_t i = tid; i < sizeof(typename P::Lds) / 16; i += BK_ACC_BLOCK) gs[i] = ls[i];
+        if constexpr (IK > 1) {
+          if (merged) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) {
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+              s_last = arrived(__hip_atomic_fetch_add(&arrive[m.bucket], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+            __syncthreads();
+            last = s_last != 0;
+            empties = s_last & 0xFFFFu;
+          }
+        }
+      } else if (!last && merged) {   // (IK > 1: merged is false otherwise)
+        __syncthreads();   // (every thread has read the peek's s_last)
+        if (tid == 0)
+          s_last = arrived(__hip_atomic_fetch_add(&arrive[m.bucket], 1u | (0x100u << mine), __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT));
+        __syncthreads();
+        last = s_last != 0;
+        empties = s_last & 0xFFFFu;
+      }
+      if constexpr (IK > 1) {
+        if (last) {
+          if (tid == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+          __syncthreads();
+          bk_merge_slabs<P>(&s, slabs + f, ni, mine, empties);
+          __syncthreads();
+          bk_finalize<P, GS_BK_FUSED_RESET != 0>(s, m.bucket, b0, st, bucket_count, s_wc);
+          reset = GS_BK_FUSED_RESET != 0;
+        }
+      }
     }
     __syncthreads();
 #ifdef GS_BK_TRACE   // tuning builds only: per item (workgroup, item, wall clock at 100 MHz, records)

@@ -138,6 +138,7 @@ struct gs_ctx {
     int S = 0, dir = -1, skip = 0;
     int64_t base = 0;
     uint64_t R = 0;
+    uint32_t n_merge = 0;   // the last window's buckets that needed the merge launches (k_bk_plan's n_multi)
   } sp[2];
   int sp_slot = 0;
   uint64_t tri_merge = 0;   // the last count's sum of d+(u) + d+(v) over its oriented edges (tri_times)
