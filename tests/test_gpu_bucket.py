@@ -13,9 +13,10 @@ import numpy as np
 import pytest
 import torch
 
+from valcheck import FLOAT_RTOL, assert_values
+
 pytestmark = pytest.mark.gpu
 
-FLOAT_RTOL = 1e-5
 BUCKET = (1, 2)   # stage_times().path of the bucket path (onesweep / direct partition)
 
 
@@ -25,12 +26,7 @@ def _dev(*arrs):
 
 def _check(got_k, got_v, want_k, want_v, dtype, op):
     assert np.array_equal(got_k.cpu().numpy(), want_k)
-    g = got_v.cpu().numpy()
-    if np.issubdtype(np.dtype(dtype), np.floating) and op == 0:
-        tol = FLOAT_RTOL * np.maximum(np.abs(want_v.astype(np.float64)), 1e-30)
-        assert not (np.abs(g.astype(np.float64) - want_v.astype(np.float64)) > tol).any()
-    else:
-        assert np.array_equal(g.view(np.uint8), want_v.view(np.uint8))
+    assert_values(got_v.cpu().numpy(), want_v, dtype, op)
 
 
 def _window(rng, n, span, offset=0, hub_frac=0.0):
@@ -468,7 +464,7 @@ def test_float_sum_presence_with_signed_zeros(engine, oracle, dtype):
     idx = np.searchsorted(rk, s)
     exact = np.bincount(idx, weights=v.astype(np.float64), minlength=len(rk))
     mag = np.bincount(idx, weights=np.abs(v.astype(np.float64)), minlength=len(rk))
-    assert not (np.abs(gv.astype(np.float64) - exact) > 1e-6 * mag + 1e-300).any()
+    assert (np.abs(gv.astype(np.float64) - exact) <= 1e-6 * mag + 1e-300).all()
 
 
 def test_reused_output_buffers(engine, oracle):

@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from valcheck import FLOAT_RTOL, assert_values
 
-FLOAT_RTOL = 1e-5
+pytestmark = pytest.mark.gpu
 
 
 def _dev(*arrs):
@@ -23,12 +23,7 @@ def _np(x):
 
 def _check(got_k, got_v, want_k, want_v, dtype, op):
     assert np.array_equal(_np(got_k), want_k)
-    g = _np(got_v)
-    if np.issubdtype(np.dtype(dtype), np.floating) and op == 0:
-        tol = FLOAT_RTOL * np.maximum(np.abs(want_v.astype(np.float64)), 1e-30)
-        assert not (np.abs(g.astype(np.float64) - want_v.astype(np.float64)) > tol).any()
-    else:
-        assert np.array_equal(g.view(np.uint8), want_v.view(np.uint8))
+    assert_values(_np(got_v), want_v, dtype, op)
 
 
 @pytest.fixture()

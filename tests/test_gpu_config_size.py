@@ -25,9 +25,9 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from valcheck import FLOAT_RTOL, assert_values  # north_star: float weight sums within 1e-5 relative
 
-FLOAT_RTOL = 1e-5  # north_star: float weight sums within 1e-5 relative
+pytestmark = pytest.mark.gpu
 
 
 def _sample_matches_oracle(oracle, src, dst, gen, first_edge, k=4096):
@@ -64,9 +64,7 @@ def test_c2_full_window_double_within_tolerance(engine, oracle):
     del src, dst, val
     rk, rv = oracle.window_reduce_mt(s_h, d_h, v_h, 1, 0)
     assert np.array_equal(gk.cpu().numpy(), rk)
-    g = gv.cpu().numpy()
-    bad = np.abs(g - rv) > FLOAT_RTOL * np.maximum(np.abs(rv), 1e-30)
-    assert not bad.any(), f"{int(bad.sum())} Double sums outside 1e-5 relative"
+    assert_values(gv.cpu().numpy(), rv, np.float64, 0)   # Double sums within 1e-5 relative
 
 
 F32_UNIT = 2.0 ** -24   # unit roundoff of Java float

@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from valcheck import FLOAT_RTOL, assert_values  # north_star: float weight sums within 1e-5 relative
+
 pytestmark = pytest.mark.gpu
 
 DIRS = {"IN": 0, "OUT": 1, "ALL": 2}
-FLOAT_RTOL = 1e-5  # north_star: float weight sums within 1e-5 relative
 
 
 def _dev(*arrs):
@@ -22,12 +23,7 @@ def _np(t):
 
 
 def _check_values(got, want, dtype, op):
-    if np.issubdtype(dtype, np.floating) and op == 0:
-        tol = FLOAT_RTOL * np.maximum(np.abs(want), 1e-30)
-        bad = np.abs(got.astype(np.float64) - want.astype(np.float64)) > tol
-        assert not bad.any(), f"{bad.sum()} float sums outside 1e-5 rel"
-    else:
-        assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), "values differ (bit-exact required)"
+    assert_values(got, want, dtype, op)
 
 
 @pytest.mark.parametrize("direction", ["OUT", "IN", "ALL"])
