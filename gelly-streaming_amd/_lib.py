@@ -48,7 +48,8 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_stream_create", "gs_stream_destroy", "gs_stream_append", "gs_stream_watermark", "gs_stream_flush",
            "gs_stream_poll", "gs_stream_stats", "gs_generate_rmat", "gs_generate_uniform", "gs_generate_zipf", "gs_generate_values", "gs_last_stage_times", "gs_last_readback",
            "gs_set_max_window_records", "gs_candidates_begin", "gs_candidates_begin_part", "gs_candidates_next", "gs_candidates_next_u32", "gs_candidates_seek",
-           "gs_candidates_vertex_range")
+           "gs_candidates_vertex_range", "gs_cont_create", "gs_cont_destroy", "gs_cont_size", "gs_cont_capacity",
+           "gs_cont_degrees", "gs_cont_vertices", "gs_cont_export", "gs_cont_import")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -250,6 +251,14 @@ def load() -> ctypes.CDLL:
                                         ctypes.POINTER(i32)]),
         "gs_candidates_seek": (st, [P, u64]),
         "gs_candidates_vertex_range": (st, [P, i64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_cont_create": (st, [P, u64, ctypes.POINTER(P)]),
+        "gs_cont_destroy": (None, [P]),
+        "gs_cont_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_cont_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_cont_degrees": (st, [P, P, ctypes.POINTER(GsEdgeBatch), i32, ctypes.POINTER(GsVertexOut)]),
+        "gs_cont_vertices": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsVertexOut)]),
+        "gs_cont_export": (st, [P, P, ctypes.POINTER(GsVertexOut)]),
+        "gs_cont_import": (st, [P, P, ctypes.POINTER(GsPartialBatch)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)

@@ -672,6 +672,12 @@ class Engine:
         U = n_out.value
         return bool(success.value), keys[:U], labels[:U], signs[:U]
 
+    # -- continuous streams (gs_continuous.hip) -------------------------------------------------------
+    def continuous(self, reserve_vertices: int = 0) -> "ContinuousState":
+        """gs_cont_create: an empty device-resident vertex table for the non-windowed operators
+        (getDegrees / getInDegrees / getOutDegrees / getVertices / numberOfVertices): one per operator."""
+        return ContinuousState(self, reserve_vertices)
+
     # -- multi-GPU keyBy halves (gs_dist.hip) --------------------------------------------------------
     def reduce_partials(self, src, dst, val, direction, op, nparts: int):
         """gs_window_reduce_partials: this slice's per-vertex partials grouped by owner (gs_owner_of).
@@ -860,3 +866,97 @@ class Engine:
         v = torch.empty(n, dtype=tdt, device=f"cuda:{self.device}")
         self._check(self._L.gs_generate_values(self.ctx, n, seed, first_edge, dtype, _ptr(v)))
         return v
+
+
+class ContinuousState:
+    """gs_cont: the state of one continuous operator of SimpleEdgeStream (include/gelly_hip.h, "continuous
+    streams") -- vertex -> records seen so far, in HBM across calls.  Feed it the stream in batches of any
+    size: the concatenated outputs depend only on the stream.  Columns are numpy arrays (results come back
+    as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
+
+    def __init__(self, engine: Engine, reserve_vertices: int = 0):
+        self.engine = engine
+        self._L = engine._L
+        h = ctypes.c_void_p()
+        engine._check(self._L.gs_cont_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.gs_cont_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _run(self, call, b, dev, R, out):
+        e = self.engine
+        if out is not None:
+            e._check_out(out, dev, (np.int64, np.int64), R)
+            keys, vals = out
+        else:
+            keys, vals = e._empty(dev, R, np.int64), e._empty(dev, R, np.int64)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(_ptr(keys), _ptr(vals), R, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        e._check(call(ctypes.byref(b), ctypes.byref(vo)))
+        n = n_out.value
+        return keys[:n], vals[:n]
+
+    def degrees(self, src, dst, direction, out=None):
+        """gs_cont_degrees: one (vertex, degree so far) per record of the batch, in arrival order -- edge i
+        gives (src[i], .) under OUT, (dst[i], .) under IN, both in that order under ALL.  out: optional
+        (vertices, degrees) int64 device tensors of at least the batch's records, reused across batches."""
+        b, keep, dev = self.engine._batch(src, dst, None)
+        R = self.engine._records(b.n, direction)
+        call = lambda pb, po: self._L.gs_cont_degrees(self.engine.ctx, self.handle, pb, int(direction), po)
+        return self._run(call, b, dev, R, out)
+
+    def vertices(self, src, dst, out=None):
+        """gs_cont_vertices: the vertices of the batch never seen before, in the order of their first
+        arrival (records expanded as ALL), and the running number of distinct vertices after each."""
+        b, keep, dev = self.engine._batch(src, dst, None)
+        call = lambda pb, po: self._L.gs_cont_vertices(self.engine.ctx, self.handle, pb, po)
+        return self._run(call, b, dev, 2 * b.n, out)
+
+    def size(self):
+        """gs_cont_size: (distinct vertices, records) seen so far."""
+        d, r = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_cont_size(self.handle, ctypes.byref(d), ctypes.byref(r)))
+        return d.value, r.value
+
+    def capacity(self):
+        """gs_cont_capacity: (slots of the table, doublings so far); load factor = size()[0] / slots."""
+        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_cont_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
+        return s.value, g.value
+
+    def export(self, device: bool = False):
+        """gs_cont_export: the checkpoint (vertices ascending, counts), numpy or (device=True) CUDA tensors."""
+        e = self.engine
+        D = self.size()[0]
+        keys, vals = e._empty(device, D, np.int64), e._empty(device, D, np.int64)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(_ptr(keys), _ptr(vals), D, ctypes.pointer(n_out), L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_cont_export(e.ctx, self.handle, ctypes.byref(vo)))
+        n = n_out.value
+        return keys[:n], vals[:n]
+
+    def load(self, keys, counts):
+        """gs_cont_import: restore a checkpoint (vertices, counts >= 1) into this, still empty, state."""
+        if _is_torch(keys):
+            import torch
+
+            counts = counts.to(torch.int64)
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int64)
+        pb, keep, dev = self.engine._partial_batch(keys, counts)
+        self.engine._check(self._L.gs_cont_import(self.engine.ctx, self.handle, ctypes.byref(pb)))

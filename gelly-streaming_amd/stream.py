@@ -1,7 +1,9 @@
 """Host-side mirror of the reference's windowed graph-stream API, backed by libgellyhip.so.
 
   SimpleEdgeStream   <- streaming/SimpleEdgeStream.java:59-540 (constructors :73-94, slice :139-171,
-                        reverse :332-341, undirected :354-365)
+                        reverse :332-341, undirected :354-365; the continuous operators getVertices :119-125,
+                        numberOfVertices :370-387, numberOfEdges :392-408, getDegrees / getInDegrees /
+                        getOutDegrees :416-442)
   GraphWindowStream  <- streaming/GraphWindowStream.java:47-183 (foldNeighbors :62, reduceOnEdges :101,
                         applyOnNeighbors :130)
 
@@ -80,6 +82,7 @@ class StreamExecutionEnvironment:
         self.device = device
         self._engine = None
         self._parallelism = 1
+        self._micro_batch = None
 
     def setParallelism(self, parallelism: int) -> "StreamExecutionEnvironment":
         """env.setParallelism: the operators' parallelism; on this path it changes what the windowed
@@ -91,6 +94,18 @@ class StreamExecutionEnvironment:
 
     def getParallelism(self) -> int:
         return self._parallelism
+
+    def setMicroBatch(self, edges: int = None) -> "StreamExecutionEnvironment":
+        """Edges per engine call of the continuous operators (getDegrees, getVertices, ...): the stream goes
+        through their device state in batches of this size (None = the whole stream at once).  The records
+        they emit do not depend on it."""
+        if edges is not None and int(edges) < 1:
+            raise ValueError("a micro-batch holds at least one edge")
+        self._micro_batch = None if edges is None else int(edges)
+        return self
+
+    def getMicroBatch(self):
+        return self._micro_batch
 
     @classmethod
     def getExecutionEnvironment(cls) -> "StreamExecutionEnvironment":
@@ -183,7 +198,8 @@ def _take(x, idx):
 
 
 class SimpleEdgeStream:
-    """streaming/SimpleEdgeStream.java — the windowed-neighbourhood part of it."""
+    """streaming/SimpleEdgeStream.java — the windowed-neighbourhood part of it and the continuous degree /
+    vertex streams."""
 
     def __init__(self, edges: EdgeColumns, context: StreamExecutionEnvironment = None,
                  timeExtractor: AscendingTimestampExtractor = None):
@@ -230,6 +246,61 @@ class SimpleEdgeStream:
     def aggregate(self, graphAggregation) -> "DataStream":
         """GraphStream.aggregate (SimpleEdgeStream.java:104-106): e.g. ConnectedComponents(mergeWindowTime)."""
         return graphAggregation.run(self)
+
+    # -- the continuous operators: one device state per call, fed in micro-batches (env.setMicroBatch) ----
+    # Records come out in the reference's order at parallelism 1 whatever env.getParallelism() says (at
+    # parallelism P the reference emits the same multiset: keyBy keeps each vertex's records in order).
+    def _micro_batches(self):
+        e = self.edges
+        n = len(e)
+        mb = self.context.getMicroBatch() or max(n, 1)
+        for a in range(0, n, mb):
+            yield e.src[a:a + mb], e.dst[a:a + mb]
+
+    def _degree_stream(self, direction: EdgeDirection) -> "DataStream":
+        out = DataStream()
+        with self.context.engine.continuous() as state:
+            for src, dst in self._micro_batches():
+                out.windows.append(WindowOutput(0, 0, state.degrees(src, dst, direction)))
+        return out
+
+    def getDegrees(self) -> "DataStream":
+        """:416-420 -> Vertex<K, Long>(vertex, degree so far) per endpoint of every edge, source first."""
+        return self._degree_stream(EdgeDirection.ALL)
+
+    def getInDegrees(self) -> "DataStream":
+        """:428-431 -> (target, in-degree so far) per edge."""
+        return self._degree_stream(EdgeDirection.IN)
+
+    def getOutDegrees(self) -> "DataStream":
+        """:439-442 -> (source, out-degree so far) per edge."""
+        return self._degree_stream(EdgeDirection.OUT)
+
+    def _vertex_stream(self, column: int) -> "DataStream":
+        out = DataStream()
+        with self.context.engine.continuous() as state:
+            for src, dst in self._micro_batches():
+                cols = state.vertices(src, dst)
+                out.windows.append(WindowOutput(0, 0, (cols[0],) if column == 0 else
+                                                ("records", [int(x) for x in _to_np(cols[1])])))
+        return out
+
+    def getVertices(self) -> "DataStream":
+        """:119-125 -> Vertex<K, NullValue>: each vertex once, at its first appearance; records (vertex,)."""
+        return self._vertex_stream(0)
+
+    def numberOfVertices(self) -> "DataStream":
+        """:370-387 -> the number of distinct vertices so far, emitted whenever it changes (bare longs)."""
+        return self._vertex_stream(1)
+
+    def numberOfEdges(self) -> "DataStream":
+        """:392-408 -> the number of edges so far, duplicates included, one per edge (bare longs): the state's
+        record counter running over the stream, no kernel."""
+        out, seen = DataStream(), 0
+        for src, _ in self._micro_batches():
+            out.windows.append(WindowOutput(0, 0, ("records", list(range(seen + 1, seen + len(src) + 1)))))
+            seen += len(src)
+        return out
 
     def slice(self, size: Time, direction: EdgeDirection = EdgeDirection.OUT) -> "GraphWindowStream":
         """:139-171 tumbling windows keyed by the neighbour-key vertex."""

@@ -492,6 +492,48 @@ typedef struct gs_signed_out {
 GS_API gs_status gs_window_bipartite(gs_ctx* ctx, const gs_edge_batch* window, const gs_signed_batch* prev,
                                      gs_signed_out* out);
 
+/* ---- continuous streams: state that outlives a window ---------------------------------------- */
+/* The non-windowed operators of SimpleEdgeStream keep one entry per vertex for the whole stream and emit a
+ * record per input record.  A gs_cont holds that state on the device: an open-addressing table from the
+ * full int64 vertex id (every value is a legal id) to a 64-bit record count, grown by doubling, plus the
+ * number of distinct vertices and of records seen.  A stream is fed to it in batches of any size; the
+ * concatenated outputs depend only on the stream, never on where it was cut.  The record order is the
+ * reference's at parallelism 1 (at parallelism P it emits the same multiset: keyBy keeps per-key order).
+ * One state serves one operator (one direction); use it from one thread at a time, with a ctx of its device.
+ * A call that returns GS_EINVAL, GS_ECAPACITY or GS_ENOMEM leaves the state exactly as it was.  Batches hold
+ * at most 2^32 - 1 records (GS_EINVAL above, as gs_window_csr: split the batch).  Outputs are complete on
+ * return (host memory) or in the order of the ctx's stream (device memory). */
+typedef struct gs_cont gs_cont;
+/* An empty state with room for reserve_vertices distinct vertices before its first growth (0 = smallest). */
+GS_API gs_status gs_cont_create(gs_ctx* ctx, uint64_t reserve_vertices, gs_cont** out);
+GS_API void gs_cont_destroy(gs_cont* state);
+/* Distinct vertices and records seen so far (either pointer may be NULL).  numberOfEdges
+ * (SimpleEdgeStream.java:392-408) is this record count running over a GS_DIR_OUT / GS_DIR_IN state: the
+ * i-th edge of a batch emits records_before + i + 1. */
+GS_API gs_status gs_cont_size(const gs_cont* state, uint64_t* distinct_vertices, uint64_t* records);
+/* The table's slots and how often it has doubled (either pointer may be NULL); load = distinct / slots. */
+GS_API gs_status gs_cont_capacity(const gs_cont* state, uint64_t* slots, uint64_t* growths);
+/* getDegrees (SimpleEdgeStream.java:416-420) = GS_DIR_ALL, getInDegrees (:428-431) = GS_DIR_IN (key = dst),
+ * getOutDegrees (:439-442) = GS_DIR_OUT (key = src): DegreeTypeSeparator :444-463 -> keyBy(0) ->
+ * DegreeMapFunction :465-482.  Edge i contributes (src[i], .) then (dst[i], .) as its direction collects
+ * them; each record carries the number of records of its vertex seen so far in the whole stream, itself
+ * included (a self-loop under ALL: (v, d + 1), (v, d + 2)).  out: keys / vals [R] in ARRIVAL order (not
+ * ascending), vals I64, R = n or 2n (ALL).  capacity < R: GS_ECAPACITY with *n_out = R. */
+GS_API gs_status gs_cont_degrees(gs_ctx* ctx, gs_cont* state, const gs_edge_batch* batch, int32_t dir,
+                                 gs_vertex_out* out);
+/* getVertices (SimpleEdgeStream.java:119-125: EmitSrcAndTarget :185-192 -> keyBy(0) -> FilterDistinctVertices
+ * :194-209) and numberOfVertices (:370-387, emitted on change only: GlobalAggregateMapper :525-539): the
+ * records expand as ALL; out holds the vertices never seen before, in this batch or an earlier one, in the
+ * order of their first arrival, with vals (I64) = the running number of distinct vertices (distinct_before
+ * + 1, + 2, ...).  capacity < 2n: GS_ECAPACITY with *n_out = 2n. */
+GS_API gs_status gs_cont_vertices(gs_ctx* ctx, gs_cont* state, const gs_edge_batch* batch, gs_vertex_out* out);
+/* Checkpoint: every (vertex, count) of the state, ascending by vertex, vals I64.  capacity < the distinct
+ * vertices: GS_ECAPACITY with *n_out = that number. */
+GS_API gs_status gs_cont_export(gs_ctx* ctx, const gs_cont* state, gs_vertex_out* out);
+/* Restore a checkpoint into an EMPTY state (GS_EINVAL otherwise): rows->keys = vertices, rows->vals = I64
+ * counts >= 1 (GS_EINVAL otherwise), any order; records = the sum of the counts. */
+GS_API gs_status gs_cont_import(gs_ctx* ctx, gs_cont* state, const gs_partial_batch* rows);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;
