@@ -16,11 +16,6 @@
 #include "gs_ops.hpp"
 #include <atomic>
 #include <chrono>
-// GS_TIMING_DOMINANT brackets the scatter and (1) the accumulate with dispatch-carried events; 0: the scatter
-// only (the accumulate's time then comes from windows timed at GS_TIMING_STAGES)
-#ifndef GS_DOM_ACCUM
-#define GS_DOM_ACCUM 1
-#endif
 
 #include "gs_bucket.hpp"
 
@@ -31,9 +26,6 @@ namespace gs {
 #endif
 #ifndef GS_BK_UNROLL
 #define GS_BK_UNROLL 8
-#endif
-#ifndef GS_BK_PLAN_EARLY
-#define GS_BK_PLAN_EARLY 1   // speculative windows of integer policies: the work items planned inside k_sp_regions
 #endif
 constexpr uint32_t BK_ITEM = 1u << GS_BK_ITEM_LOG;
 
@@ -202,8 +194,9 @@ gs_status bucket_accumulate(gs_ctx* c, Src rs, uint64_t R, uint32_t nb, int64_t 
   BkStage st{c->keysA.as<uint32_t>(), c->valsA.p,
              (std::is_same_v<P, BkDeg> || std::is_same_v<P, BkDeg32>) ? c->aux.as<int64_t>() : nullptr};
   auto* slabs = c->bk_slabs.as<typename P::Lds>();
-  // the direct path's accumulate (ev0 2) is a dominant kernel: its own start (pass_ev[7]) and stop events
-  const bool dom = GS_DOM_ACCUM && ev0 == 2 && c->timing == GS_TIMING_DOMINANT;
+  // the direct path's accumulate (ev0 2) is a dominant kernel (GS_TIMING_DOMINANT brackets the scatter and the
+  // accumulate with dispatch-carried events): its own start (pass_ev[7]) and stop events
+  const bool dom = ev0 == 2 && c->timing == GS_TIMING_DOMINANT;
   launch_dominant(c, dom ? c->pass_ev[7] : nullptr, dom ? c->pass_ev[ev0 + 1] : nullptr, k_bk_accum<P, Src, GS_BK_UNROLL>,
                   dim3(c->n_cu * GS_BK_ACC_PER_CU), dim3(BK_ACC_BLOCK), rs, (const BkItem*)c->bk_items.as<BkItem>(),
                   (const uint32_t*)(meta + BkMeta::BSTART), slabs, st, meta + BkMeta::BCOUNT,
@@ -336,7 +329,7 @@ void bucket_times(gs_ctx* c, int path, int passes, int launches, uint32_t key_bi
   if (!all) {   // only the events stage_event recorded at this level
     if (c->timing == GS_TIMING_DOMINANT && path == 2) {   // the scatter and the accumulate (launch_dominant)
       if (passes) t.pass_ms[1] = event_ms(c->pass_ev[1], c->pass_ev[2]);
-      if (GS_DOM_ACCUM) t.pass_ms[2] = event_ms(c->pass_ev[7], c->pass_ev[3]);
+      t.pass_ms[2] = event_ms(c->pass_ev[7], c->pass_ev[3]);
     }
   }
 }
@@ -364,17 +357,213 @@ gs_status ensure_stage(gs_ctx* c, uint64_t R) {
 // window of this ctx had more than 1/8 escapes; every other op through k_dp_scatter.
 // Events: ev[1] / pass_ev[0] after the histogram; pass_ev[0..2] around the offset scans and the
 // scatter; then accumulate / merge / emit.
+
+template <class P>
+constexpr bool BK_CAN_PACK = P::PAY == PAY_VAL && !P::REL && std::is_integral_v<typename P::A>;
+template <class P, int ITEMS>
+constexpr bool BK_SPEC_OK = (BK_CAN_PACK<P> && ITEMS == PK_ITEMS) || ITEMS == DP_ITEMS;
+
+// a direct-path window: its inputs, and the geometry its attempts run against (predicted, then measured)
+template <class P>
+struct DirectWin {
+  const int64_t *src, *dst;
+  const void* val;
+  uint64_t n, R;
+  uint32_t nt, nch;   // k_dp_hist's tiles and their chunks
+  typename P::Out o;
+  bool pack;
+  uint32_t item_recs;
+  int64_t base;
+  uint32_t nb;
+};
+
+// each XCD slot's share of a speculative window's records: slot x owns the full tiles [x·per, (x+1)·per) of `te`
+// edges, the partial last tile runs in slot 0 (k_sp_scatter_pack).  xmask 0: segment 0 is the whole region
+template <int DIR>
+SpSlots sp_slot_shares(uint64_t n, uint64_t te, uint32_t xmask) {
+  const uint64_t rpe = DIR == DIR_ALL ? 2 : 1, R = rpe * n;
+  SpSlots slots{};
+  if (!xmask) {
+    for (uint32_t x = 1; x <= SP_NSEG; ++x) slots.pre[x] = (uint32_t)R;
+    return slots;
+  }
+  const uint64_t tr = rpe * te, nfull = n / te, per = (nfull + 7) / 8;
+  uint64_t acc = 0;
+  for (uint32_t x = 0; x < SP_NSEG; ++x) {
+    slots.pre[x] = (uint32_t)acc;
+    const uint64_t lo = std::min<uint64_t>(nfull, x * per), hi = std::min<uint64_t>(nfull, (x + 1) * per);
+    acc += (hi - lo) * tr + (x == 0 ? R - nfull * tr : 0);
+  }
+  slots.pre[SP_NSEG] = (uint32_t)acc;   // == R
+  return slots;
+}
+
+// One speculative attempt: regions from the previous window's counts (integer policies: and the items, from the
+// regions' capacities) -> the scatter reserves runs with atomics -> (other policies: items from the cursors)
+// -> accumulate, which also reports the counts the next window predicts from.  A deferred window
+// (gs_window_reduce_dist) returns GS_PENDING_LOCAL right after the launches; otherwise GS_OK after the wait, and
+// the read-back block says hit or miss (host_small[2]).
+template <class P, int DIR, int ITEMS>
+gs_status spec_attempt(gs_ctx* c, const DirectWin<P>& w, uint64_t cap, bool defer) {
+  using Raw = typename P::Raw;
+  using Load = typename P::Load;
+  constexpr int S = P::S;
+  char* sm = c->small.as<char>();
+  uint32_t* meta = c->bk_meta.as<uint32_t>();
+  auto& sp = c->sp[c->sp_slot];
+  auto* mm = (unsigned long long*)(sm + SM_BK_MM);
+  auto* esc = (unsigned long long*)(sm + SM_BK_ESC);
+  uint32_t* rel_bad = (uint32_t*)(sm + SM_BK_N) + 3;
+  uint32_t* cur = c->sp_cur.as<uint32_t>();
+  uint32_t* kp = c->keysB.as<uint32_t>();
+  uint16_t* k16 = c->keysB.as<uint16_t>();
+  Raw* vpart = P::HAS_V ? c->valsB.as<Raw>() : nullptr;
+  const uint64_t n = w.n;
+  const uint32_t nb = w.nb;
+  // merges (slot 1) speculate with ONE segment per bucket: their rows are sender runs sorted by
+  // vertex, so a tile holds few buckets and a bucket's records come from the tiles of one XCD slot
+  // -- proportional per-slot segments would overflow.  A tile reserves one run per bucket it
+  // touches (a handful), so the single cursor sees few atomics.
+  const uint32_t xmask = c->sp_slot == 0 ? 7u : 0u;
+  // the speculative scatter's tile: k_sp_scatter_pack (SPK_BLOCK x SPK_ITEMS) or k_sp_scatter (SPU_BLOCK x SPU_ITEMS)
+  const SpSlots slots = sp_slot_shares<DIR>(n, w.pack ? spk_tile_edges<DIR>() : spu_tile_edges<DIR>(), xmask);
+  // the previous window had no bucket for the merge launches: none are launched, and the plan counts one
+  // that turns up as a miss
+  const bool no_merge = bk_inline_k<P>() > 1 && sp.n_merge == 0;
+  // integer policies: the items planned from the regions' capacities inside k_sp_regions, no launch
+  // between the scatter and the accumulate (float sums keep k_bk_plan over the cursors: their items, and
+  // with them the order of their merges, stay what they were)
+  constexpr bool PLAN_EARLY = bk_inline_k<P>() > 1;
+  BkPlanOut po{};
+  if (PLAN_EARLY) GS_TRY(plan_out<P>(c, cap, nb, w.item_recs, nullptr, nullptr, nullptr, &po));
+  hipLaunchKernelGGL(k_sp_regions, dim3(1), dim3(BK_PLAN_BLOCK), 0, c->stream, (const uint32_t*)sp.tot.as<uint32_t>(),
+                     nb, sp.R, w.R, meta + BkMeta::BSTART, cur, slots, mm, esc, w.item_recs, bk_inline_k<P>(), no_merge,
+                     po);
+  if constexpr (P::REL) GS_HIP(hipMemsetAsync(rel_bad, 0, 4, c->stream));
+  stage_event(c, c->ev[1]);
+  stage_event(c, c->pass_ev[0]);
+  stage_event(c, c->pass_ev[1]);
+  const BaseSrc<Load, DIR, P::PAY> ls{w.src, w.dst, (const Load*)w.val, w.base};
+  hipEvent_t e0 = c->pass_ev[1], e1 = c->pass_ev[2];
+  const uint32_t trash = (uint32_t)cap;
+  // the bucket tables sized for the window's buckets (1024: 8 KiB less LDS, one bucket per thread)
+  auto with_nb = [&](auto launch) {
+    if (nb <= 1024) launch(std::integral_constant<int, 1024>{});
+    else launch(std::integral_constant<int, BK_MAXB>{});
+  };
+  if constexpr (BK_CAN_PACK<P> && ITEMS == PK_ITEMS) {
+    if (w.pack)
+      with_nb([&](auto NB) {
+        launch_dominant(c, e0, e1, k_sp_scatter_pack<Load, DIR, NB()>, dim3(spk_grid<DIR>(n)), dim3(SPK_BLOCK), ls, n, S,
+                        nb, cur, kp, vpart, trash, mm, esc, xmask);
+      });
+  }
+  if constexpr (ITEMS == DP_ITEMS) {
+    if (!w.pack)
+      with_nb([&](auto NB) {
+        launch_dominant(c, e0, e1, k_sp_scatter<Load, DIR, P::PAY, Raw, P::REL, NB()>, dim3(spu_grid<DIR>(n)),
+                        dim3(SPU_BLOCK), ls, n, S, nb, cur, k16, vpart, trash, rel_bad, mm, xmask);
+      });
+  }
+  GS_HIP(hipGetLastError());
+  stage_event(c, c->pass_ev[2]);
+  stage_event(c, c->ev[2]);
+  if (!PLAN_EARLY) GS_TRY(launch_plan<P>(c, cap, nb, 0, 0, w.item_recs, cur, sp.tot.as<uint32_t>(), mm, no_merge));
+  uint32_t* counts = PLAN_EARLY ? sp.tot.as<uint32_t>() : nullptr;
+  if (w.pack)
+    GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{kp, vpart}, cap, nb, w.base, w.o, 2, cur, no_merge, counts)));
+  else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, cap, nb, w.base, w.o, 2, cur, no_merge, counts)));
+  if (defer) return GS_PENDING_LOCAL;
+  return bucket_wait(c);
+}
+
+// One histogram attempt against (w.base, w.nb): the tiles' bucket counts, the offsets, one scatter (part: more
+// than one bucket), accumulate and the wait.  It measures the vertex range and counts the keys outside the
+// predicted one (host_small[0..2]); run with the measured range it cannot miss.
+template <class P, int DIR, int ITEMS>
+gs_status hist_attempt(gs_ctx* c, const DirectWin<P>& w, bool part) {
+  using Raw = typename P::Raw;
+  using Load = typename P::Load;
+  constexpr int S = P::S;
+  char* sm = c->small.as<char>();
+  uint32_t* meta = c->bk_meta.as<uint32_t>();
+  uint16_t* cnt = c->dp_cnt.as<uint16_t>();
+  uint32_t* csum = c->dp_csum.as<uint32_t>();
+  uint16_t* k16 = c->keysB.as<uint16_t>();
+  Raw* vpart = P::HAS_V ? c->valsB.as<Raw>() : nullptr;
+  uint32_t* rel_bad = (uint32_t*)(sm + SM_BK_N) + 3;
+  auto* mm = (unsigned long long*)(sm + SM_BK_MM);
+  const uint64_t n = w.n, R = w.R;
+  const uint32_t nb = w.nb, nt = w.nt, nch = w.nch;
+  const int64_t base = w.base;
+  const bool pack = w.pack;
+  // 1. per-tile bucket counts against the predicted base and width (the window's one read of
+  //    the keys before the scatter) + the measured range and the keys outside the prediction
+  GS_TRY((launch_dp_hist<DIR, ITEMS>(c, w.src, w.dst, n, nt, base, S, nb)));
+  GS_HIP(hipMemsetAsync(sm + SM_BK_ESC, 0, 8, c->stream));
+  stage_event(c, c->ev[1]);
+  stage_event(c, c->pass_ev[0]);
+
+  // 2. offsets: chunk counts, per-bucket spine (-> meta[HIST] totals), plan, per-tile offsets
+  const dim3 g2((nb + 255) / 256, nch);
+  hipLaunchKernelGGL(k_dp_up, g2, dim3(256), 0, c->stream, cnt, nt, nb, csum);
+  hipLaunchKernelGGL(k_dp_spine, dim3((nb + 63) / 64), dim3(1024), 0, c->stream, csum, nch, nb, meta + BkMeta::HIST);
+  GS_HIP(hipGetLastError());
+  GS_TRY(launch_plan<P>(c, R, nb, 0, 0, w.item_recs, nullptr,
+                        BK_SPEC_OK<P, ITEMS> ? c->sp[c->sp_slot].tot.as<uint32_t>() : nullptr));
+  if (part) {
+    hipLaunchKernelGGL(k_dp_down, g2, dim3(256), 0, c->stream, cnt, csum, meta + BkMeta::BSTART, nt, nb,
+                       c->dp_off.as<uint32_t>());
+    GS_HIP(hipGetLastError());
+  }
+  stage_event(c, c->pass_ev[1], !part);   // (a partitioned window's scatter carries its own events)
+
+  // 3. the scatter: bucket-local index + payload in bucket order
+  if constexpr (P::REL) {
+    if (!part) return GS_RETRY_WIDE;   // offsets are checked by the scatter only
+  }
+  const BaseSrc<Load, DIR, P::PAY> ls{w.src, w.dst, (const Load*)w.val, base};
+  if (part) {
+    const unsigned grid = dp_scatter_grid<DIR, ITEMS>(n);
+    const uint32_t* off = c->dp_off.as<uint32_t>();
+    const auto* mmc = (const unsigned long long*)mm;
+    if constexpr (BK_CAN_PACK<P>) {
+      if (pack) {
+        launch_dominant(c, c->pass_ev[1], c->pass_ev[2], k_dp_scatter_pack<Load, DIR, ITEMS>, dim3(grid), dim3(DP_BLOCK),
+                        ls, n, S, nb, off, c->keysB.as<uint32_t>(), vpart, mmc, (unsigned long long*)(sm + SM_BK_ESC));
+        GS_HIP(hipGetLastError());
+      }
+    }
+    if constexpr (ITEMS == DP_ITEMS) if (!pack) {
+      if constexpr (P::REL) GS_HIP(hipMemsetAsync(rel_bad, 0, 4, c->stream));
+      launch_dominant(c, c->pass_ev[1], c->pass_ev[2], k_dp_scatter<Load, DIR, P::PAY, Raw, P::REL>, dim3(grid),
+                      dim3(DP_BLOCK), ls, n, S, nb, c->dp_off.as<uint32_t>(), k16, vpart, rel_bad, mmc);
+      GS_HIP(hipGetLastError());
+    }
+  }
+  stage_event(c, c->pass_ev[2], !part);
+  stage_event(c, c->ev[2]);
+
+  // 4-6. accumulate, merge, emit; one read-back
+  if (part) {
+    if (pack) GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{c->keysB.as<uint32_t>(), vpart}, R, nb, base, w.o, 2)));
+    else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, R, nb, base, w.o, 2)));
+  } else if constexpr (!P::REL) {
+    const BaseSrc<Raw, DIR, P::PAY> es{w.src, w.dst, (const Raw*)w.val, base};
+    GS_TRY((bucket_accumulate<P>(c, es, R, nb, base, w.o, 2)));
+  }
+  return bucket_wait(c);
+}
+
 template <class P, int DIR, int ITEMS>
 gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, const void* val, uint64_t n,
                           typename P::Out o, uint64_t* U, bool pack) {
   using Raw = typename P::Raw;
   constexpr int S = P::S;
-  constexpr bool CAN_PACK = P::PAY == PAY_VAL && !P::REL && std::is_integral_v<typename P::A>;
-  char* sm = c->small.as<char>();
+  constexpr bool CAN_PACK = BK_CAN_PACK<P>, SPEC_OK = BK_SPEC_OK<P, ITEMS>;
   const uint64_t R = (DIR == DIR_ALL) ? 2 * n : n;
   GS_TRY(ensure(c, c->bk_meta, BkMeta::TOTAL * 4, true));
   GS_TRY(ensure_cu(c));
-  uint32_t* meta = c->bk_meta.as<uint32_t>();
   constexpr uint32_t TE = dp_tile_edges<DIR, ITEMS>();
   const uint32_t nt = (uint32_t)((n + TE - 1) / TE);
   const uint32_t nch = (nt + DP_CHUNK - 1) / DP_CHUNK;
@@ -382,26 +571,20 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
   GS_TRY(ensure(c, c->dp_csum, (size_t)nch * BK_MAXB * 4));
   GS_TRY(ensure(c, c->dp_off, (size_t)nt * BK_MAXB * 4));
   GS_TRY(ensure_stage<P>(c, R));
-  int64_t base = c->bk_base;
-  uint32_t nb = c->bk_nbp ? c->bk_nbp : (uint32_t)BK_MAXB;
-  const uint32_t item_recs = item_records(c, R);
+  DirectWin<P> w{src, dst, val, n, R, nt, nch, o, pack, item_records(c, R), c->bk_base,
+                 c->bk_nbp ? c->bk_nbp : (uint32_t)BK_MAXB};
+  int64_t& base = w.base;
+  uint32_t& nb = w.nb;
   // speculative partition: windows whose bucket counts the previous bucket-path window of this ctx
   // measured in the same geometry (base, S, direction); packed records through k_sp_scatter_pack, the
   // others through k_sp_scatter
-  constexpr bool SPEC_OK = (CAN_PACK && ITEMS == PK_ITEMS) || ITEMS == DP_ITEMS;
   bool spec = false, spec_missed = false;
   uint64_t cap = R;
-  // the speculative scatter's tile: k_sp_scatter_pack (SPK_BLOCK x SPK_ITEMS) or k_sp_scatter (DP_TILE)
-  const uint64_t TRASH = std::max<uint64_t>(SPK_TILE, SPU_TILE);
-  const uint64_t SPTE = !pack ? spu_tile_edges<DIR>() : spk_tile_edges<DIR>();
+  const uint64_t TRASH = std::max<uint64_t>(SPK_TILE, SPU_TILE);   // the larger of the speculative scatters' tiles
   auto& sp = c->sp[c->sp_slot];
   if constexpr (SPEC_OK) {
     GS_TRY(ensure(c, sp.tot, BK_MAXB * 4, true));
     GS_TRY(ensure(c, c->sp_cur, SP_CUR_WORDS * 4));
-    // merges (slot 1) speculate with ONE segment per bucket: their rows are sender runs sorted by
-    // vertex, so a tile holds few buckets and a bucket's records come from the tiles of one XCD slot
-    // -- proportional per-slot segments would overflow.  A tile reserves one run per bucket it
-    // touches (a handful), so the single cursor sees few atomics.
     spec = !(c->flags & GS_FLAG_NO_SPEC) && sp.ok && sp.skip == 0 && sp.base == base && sp.S == S &&
            sp.dir == DIR && nb > 1 && sp_capacity(R, nb) + TRASH < (1ull << 32);   // u32 positions + trash
     if (sp.skip > 0) --sp.skip;
@@ -410,184 +593,38 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
       GS_TRY(ensure_stage<P>(c, cap + TRASH));   // + the trash area of dropped runs
     }
   }
-  uint16_t* cnt = c->dp_cnt.as<uint16_t>();
-  uint32_t* csum = c->dp_csum.as<uint32_t>();
-  uint16_t* k16 = c->keysB.as<uint16_t>();
-  Raw* vpart = P::HAS_V ? c->valsB.as<Raw>() : nullptr;
-  uint32_t* rel_bad = (uint32_t*)(sm + SM_BK_N) + 3;
-  auto* mm = (unsigned long long*)(sm + SM_BK_MM);
-  bool part = false;
+  bool part = false, hit = false;
   int64_t kmin = 0, kmax = 0;
-  for (int attempt = 0;; ++attempt) {
-    if constexpr (SPEC_OK) {
+  if constexpr (SPEC_OK) {
+    if (spec) {
       // gs_window_reduce_dist's deferred window (OwnerEmit::defer; not the 32-bit-neighbour policies, whose
       // read-back can still ask for the wide one): the launches return at once, the resumed call skips them
       const bool defer = !P::REL && c->oe.nparts && c->oe.defer;
-      if (spec && attempt == 0 && defer && c->oe.resume) {
-        c->oe.resume = false;
-        if (!c->host_small[2]) {   // hit
-          kmin = (int64_t)((uint64_t)base + (c->host_small[0] << S));
-          kmax = (int64_t)((uint64_t)base + (c->host_small[1] << S) + ((1ull << S) - 1));
-          part = true;
-          break;
-        }
-        sp.skip = 8;
-        spec = false;
-        spec_missed = true;
-        continue;
-      }
-      if (spec && attempt == 0) {
-        // regions from the previous window's counts (integer policies: and the items, from the regions'
-        // capacities) -> the scatter reserves runs with atomics -> (other policies: items from the cursors)
-        // -> accumulate, which also reports the counts the next window predicts from
-        // each XCD slot's share of the records (k_sp_scatter_pack: slot x owns full tiles [x·per, (x+1)·per),
-        // the partial last tile runs in slot 0)
-        SpSlots slots{};
-        const uint32_t xmask = c->sp_slot == 0 ? 7u : 0u;
-        if (!xmask) {   // segment 0 = the whole region
-          for (uint32_t x = 1; x <= SP_NSEG; ++x) slots.pre[x] = (uint32_t)R;
-        } else {
-          const uint64_t tr = (DIR == DIR_ALL ? 2 : 1) * SPTE, nfull = n / SPTE, per = (nfull + 7) / 8;
-          uint64_t acc = 0;
-          for (uint32_t x = 0; x < SP_NSEG; ++x) {
-            slots.pre[x] = (uint32_t)acc;
-            const uint64_t lo = std::min<uint64_t>(nfull, SP_NSEG == 1 ? 0 : x * per);
-            const uint64_t hi = SP_NSEG == 1 ? nfull : std::min<uint64_t>(nfull, (x + 1) * per);
-            acc += (hi - lo) * tr + (x == 0 ? R - nfull * tr : 0);
-          }
-          slots.pre[SP_NSEG] = (uint32_t)acc;   // == R
-        }
-        // the previous window had no bucket for the merge launches: none are launched, and the plan counts one
-        // that turns up as a miss
-        const bool no_merge = bk_inline_k<P>() > 1 && sp.n_merge == 0;
-        // integer policies: the items planned from the regions' capacities inside k_sp_regions, no launch
-        // between the scatter and the accumulate (float sums keep k_bk_plan over the cursors: their items, and
-        // with them the order of their merges, stay what they were)
-        constexpr bool PLAN_EARLY = GS_BK_PLAN_EARLY && bk_inline_k<P>() > 1;
-        BkPlanOut po{};
-        if (PLAN_EARLY) GS_TRY(plan_out<P>(c, cap, nb, item_recs, nullptr, nullptr, nullptr, &po));
-        hipLaunchKernelGGL(k_sp_regions, dim3(1), dim3(BK_PLAN_BLOCK), 0, c->stream, (const uint32_t*)sp.tot.as<uint32_t>(),
-                           nb, sp.R, R, meta + BkMeta::BSTART, c->sp_cur.as<uint32_t>(), slots, mm,
-                           (unsigned long long*)(sm + SM_BK_ESC), item_recs, bk_inline_k<P>(), no_merge, po);
-        if constexpr (P::REL) GS_HIP(hipMemsetAsync(rel_bad, 0, 4, c->stream));
-        stage_event(c, c->ev[1]);
-        stage_event(c, c->pass_ev[0]);
-        stage_event(c, c->pass_ev[1]);
-        using Load = typename P::Load;
-        const BaseSrc<Load, DIR, P::PAY> ls{src, dst, (const Load*)val, base};
-        uint32_t* cur = c->sp_cur.as<uint32_t>();
-        hipEvent_t e0 = c->pass_ev[1], e1 = c->pass_ev[2];
-        uint32_t* kp = c->keysB.as<uint32_t>();
-        auto* esc = (unsigned long long*)(sm + SM_BK_ESC);
-        const uint32_t trash = (uint32_t)cap;
-        if constexpr (CAN_PACK && ITEMS == PK_ITEMS) {
-          // the bucket tables sized for the window's buckets (1024: 8 KiB less LDS, one bucket per thread)
-          if (pack && nb <= 1024)
-            launch_dominant(c, e0, e1, k_sp_scatter_pack<Load, DIR, 1024>, dim3(spk_grid<DIR>(n)), dim3(SPK_BLOCK), ls, n,
-                            S, nb, cur, kp, vpart, trash, mm, esc, xmask);
-          else if (pack)
-            launch_dominant(c, e0, e1, k_sp_scatter_pack<Load, DIR, BK_MAXB>, dim3(spk_grid<DIR>(n)), dim3(SPK_BLOCK), ls,
-                            n, S, nb, cur, kp, vpart, trash, mm, esc, xmask);
-        }
-        if constexpr (ITEMS == DP_ITEMS) {
-          if (!pack) {
-            if (nb <= 1024)
-              launch_dominant(c, e0, e1, k_sp_scatter<Load, DIR, P::PAY, Raw, P::REL, 1024>, dim3(spu_grid<DIR>(n)),
-                              dim3(SPU_BLOCK), ls, n, S, nb, cur, k16, vpart, trash, rel_bad, mm, xmask);
-            else
-              launch_dominant(c, e0, e1, k_sp_scatter<Load, DIR, P::PAY, Raw, P::REL, BK_MAXB>, dim3(spu_grid<DIR>(n)),
-                              dim3(SPU_BLOCK), ls, n, S, nb, cur, k16, vpart, trash, rel_bad, mm, xmask);
-          }
-        }
-        GS_HIP(hipGetLastError());
-        stage_event(c, c->pass_ev[2]);
-        stage_event(c, c->ev[2]);
-        if (!PLAN_EARLY) GS_TRY(launch_plan<P>(c, cap, nb, 0, 0, item_recs, cur, sp.tot.as<uint32_t>(), mm, no_merge));
+      if (defer && c->oe.resume) c->oe.resume = false;
+      else GS_TRY((spec_attempt<P, DIR, ITEMS>(c, w, cap, defer)));
+      hit = !c->host_small[2];
+      if (hit) {   // every key in the range; the accumulate reported the occupied buckets
+        kmin = (int64_t)((uint64_t)base + (c->host_small[0] << S));
+        kmax = (int64_t)((uint64_t)base + (c->host_small[1] << S) + ((1ull << S) - 1));
         part = true;
-        uint32_t* counts = PLAN_EARLY ? sp.tot.as<uint32_t>() : nullptr;
-        if (pack)
-          GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{c->keysB.as<uint32_t>(), vpart}, cap, nb, base, o, 2, cur, no_merge,
-                                       counts)));
-        else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, cap, nb, base, o, 2, cur, no_merge, counts)));
-        if (defer) return GS_PENDING_LOCAL;
-        GS_TRY(bucket_wait(c));
-        if (!c->host_small[2]) {   // hit: every key in the range; the plan reported the occupied buckets
-          kmin = (int64_t)((uint64_t)base + (c->host_small[0] << S));
-          kmax = (int64_t)((uint64_t)base + (c->host_small[1] << S) + ((1ull << S) - 1));
-          break;
-        }
+      } else {
         // missed (a run past its segment, or a key outside the range): rerun through the histogram,
         // which measures the range (and reruns once more if the prediction missed it); the next 8
         // windows do not speculate
         sp.skip = 8;
         spec = false;
         spec_missed = true;
-        continue;
       }
     }
-    // 1. per-tile bucket counts against the predicted base and width (the window's one read of
-    //    the keys before the scatter) + the measured range and the keys outside the prediction
-    GS_TRY((launch_dp_hist<DIR, ITEMS>(c, src, dst, n, nt, base, S, nb)));
-    GS_HIP(hipMemsetAsync(sm + SM_BK_ESC, 0, 8, c->stream));
-    stage_event(c, c->ev[1]);
-    stage_event(c, c->pass_ev[0]);
-
-    // 2. offsets: chunk counts, per-bucket spine (-> meta[HIST] totals), plan, per-tile offsets
+  }
+  for (int attempt = 0; !hit; ++attempt) {   // at most two: the second runs with the measured range
     part = nb > 1;
-    const dim3 g2((nb + 255) / 256, nch);
-    hipLaunchKernelGGL(k_dp_up, g2, dim3(256), 0, c->stream, cnt, nt, nb, csum);
-    hipLaunchKernelGGL(k_dp_spine, dim3((nb + 63) / 64), dim3(1024), 0, c->stream, csum, nch, nb, meta + BkMeta::HIST);
-    GS_HIP(hipGetLastError());
-    GS_TRY(launch_plan<P>(c, R, nb, 0, 0, item_recs, nullptr, SPEC_OK ? sp.tot.as<uint32_t>() : nullptr));
-    if (part) {
-      hipLaunchKernelGGL(k_dp_down, g2, dim3(256), 0, c->stream, cnt, csum, meta + BkMeta::BSTART, nt, nb,
-                         c->dp_off.as<uint32_t>());
-      GS_HIP(hipGetLastError());
-    }
-    stage_event(c, c->pass_ev[1], !part);   // (a partitioned window's scatter carries its own events)
-
-    // 3. the scatter: bucket-local index + payload in bucket order
-    if constexpr (P::REL) {
-      if (!part) return GS_RETRY_WIDE;   // offsets are checked by the scatter only
-    }
-    using Load = typename P::Load;
-    const BaseSrc<Load, DIR, P::PAY> ls{src, dst, (const Load*)val, base};
-    if (part) {
-      const unsigned grid = dp_scatter_grid<DIR, ITEMS>(n);
-      const uint32_t* off = c->dp_off.as<uint32_t>();
-      const auto* mmc = (const unsigned long long*)mm;
-      if constexpr (CAN_PACK) {
-        if (pack) {
-          launch_dominant(c, c->pass_ev[1], c->pass_ev[2], k_dp_scatter_pack<Load, DIR, ITEMS>, dim3(grid), dim3(DP_BLOCK),
-                          ls, n, S, nb, off, c->keysB.as<uint32_t>(), vpart, mmc, (unsigned long long*)(sm + SM_BK_ESC));
-          GS_HIP(hipGetLastError());
-        }
-      }
-      if constexpr (ITEMS == DP_ITEMS) if (!pack) {
-        if constexpr (P::REL) GS_HIP(hipMemsetAsync(rel_bad, 0, 4, c->stream));
-        launch_dominant(c, c->pass_ev[1], c->pass_ev[2], k_dp_scatter<Load, DIR, P::PAY, Raw, P::REL>, dim3(grid),
-                        dim3(DP_BLOCK), ls, n, S, nb, c->dp_off.as<uint32_t>(), k16, vpart, rel_bad, mmc);
-        GS_HIP(hipGetLastError());
-      }
-    }
-    stage_event(c, c->pass_ev[2], !part);
-    stage_event(c, c->ev[2]);
-
-    // 4-6. accumulate, merge, emit; one read-back
-    if (part) {
-      if (pack) GS_TRY((bucket_accumulate<P>(c, PackSrc<Raw>{c->keysB.as<uint32_t>(), vpart}, R, nb, base, o, 2)));
-      else GS_TRY((bucket_accumulate<P>(c, PartSrc<Raw>{k16, vpart}, R, nb, base, o, 2)));
-    } else if constexpr (!P::REL) {
-      const BaseSrc<Raw, DIR, P::PAY> es{src, dst, (const Raw*)val, base};
-      GS_TRY((bucket_accumulate<P>(c, es, R, nb, base, o, 2)));
-    }
-    GS_TRY(bucket_wait(c));
+    GS_TRY((hist_attempt<P, DIR, ITEMS>(c, w, part)));
     kmin = key_min(c->host_small);
     kmax = key_max(c->host_small);
     if ((((uint64_t)kmax - (uint64_t)kmin) >> S) >= (uint64_t)BK_MAXB) return GS_EUNSUPPORTED;
     if (!c->host_small[2]) break;
-    if (attempt > (spec_missed ? 1 : 0))
-      return set_error(c, GS_EDEVICE, "bucket path: keys outside the measured vertex range");
+    if (attempt > 0) return set_error(c, GS_EDEVICE, "bucket path: keys outside the measured vertex range");
     base = predict_base(kmin, kmax, S);   // missed prediction: rerun with the measured range
     nb = (uint32_t)((((uint64_t)kmax - (uint64_t)base) >> S) + 1);
   }
@@ -637,8 +674,7 @@ gs_status bucket_direct_t(gs_ctx* c, const int64_t* src, const int64_t* dst, con
 template <class P, int DIR>
 gs_status bucket_direct(gs_ctx* c, const int64_t* src, const int64_t* dst, const void* val, uint64_t n,
                         typename P::Out o, uint64_t* U) {
-  constexpr bool CAN_PACK = P::PAY == PAY_VAL && !P::REL && std::is_integral_v<typename P::A>;
-  if constexpr (CAN_PACK) {
+  if constexpr (BK_CAN_PACK<P>) {
     if (c->bk_wide_vals[c->sp_slot] <= 0 && !(c->flags & GS_FLAG_NO_PACK))
       return bucket_direct_t<P, DIR, PK_ITEMS>(c, src, dst, val, n, o, U, true);
   }

@@ -59,9 +59,6 @@ template <class P>
 __host__ __device__ constexpr uint32_t bk_inline_k() {
   return std::is_integral_v<typename P::A> && GS_BK_INLINE_K > 1 ? (uint32_t)GS_BK_INLINE_K : 0u;
 }
-#ifndef GS_BK_FUSED_RESET
-#define GS_BK_FUSED_RESET 1   // k_bk_accum: each wave resets its own finalized entries (no block-wide init pass)
-#endif
 #ifndef GS_BK_S8
 #define GS_BK_S8 14   // 2^S vertices per bucket with 8-byte accumulators (BkVal)
 #endif
@@ -115,13 +112,7 @@ struct BkPlanOut {
 // predicted count with its relative slack, 4-aligned) gives segment x its share of T,
 // T·pre[x] / pre[SP_NSEG] (pre[x] = the window's records in the tiles of slots before x, i.e.
 // k_sp_scatter_pack's tile -> slot map), plus SP_PADSEG records of absolute slack.
-#ifndef GS_SP_XCD
-#define GS_SP_XCD 1
-#endif
-constexpr uint32_t SP_NSEG = GS_SP_XCD ? 8 : 1;
-#ifndef GS_SP_MATCH
-#define GS_SP_MATCH 1   // k_sp_scatter (folds): wave-aggregated ranking for the first lane's bucket
-#endif
+constexpr uint32_t SP_NSEG = 8;
 constexpr uint32_t SP_PAD = 1024;                  // absolute slack per bucket
 constexpr uint32_t SP_PADSEG = SP_PAD / SP_NSEG;   // ... per segment
 static_assert(SP_PADSEG % 4 == 0, "segment starts stay 4-aligned");
@@ -596,9 +587,6 @@ __device__ __forceinline__ uint32_t bk_block_scan(uint32_t x, uint32_t* s_w, uin
   return off + inc - x;
 }
 
-#ifndef GS_BK_LPT
-#define GS_BK_LPT 1
-#endif
 constexpr int BK_LPT_CLASSES = 64;
 // the work items of buckets 2 tid and 2 tid + 1 (c0, c1 records; one block of BK_PLAN_BLOCK threads): a bucket
 // of cnt records is split into ceil(cnt / item_recs) items; multi-item buckets get consecutive slabs.  A bucket
@@ -616,10 +604,9 @@ __device__ __forceinline__ uint32_t bk_plan_items(uint32_t c0, uint32_t c1, uint
   const uint32_t lk = max(1u, inline_k);   // more items than this: a launched merge
   const uint32_t g0 = i0 > lk ? 1u : 0u, g1 = i1 > lk ? 1u : 0u;
   uint32_t n_items, n_slabs, n_multi;
-  const uint32_t first0 = bk_block_scan(i0 + i1, s_w, n_items);
+  bk_block_scan(i0 + i1, s_w, n_items);
   const uint32_t slab0 = bk_block_scan(m0 + m1, s_w, n_slabs);
   const uint32_t mb0 = bk_block_scan(g0 + g1, s_w, n_multi);
-#if GS_BK_LPT
   // claim order: largest items first (k_bk_accum's workgroups take items from a counter, so the small
   // ones fill the gaps at the end instead of a large one starting last): a counting sort over
   // BK_LPT_CLASSES size classes, descending; the order within a class is free
@@ -648,8 +635,7 @@ __device__ __forceinline__ uint32_t bk_plan_items(uint32_t c0, uint32_t c1, uint
     s_cls[tid] = wave_inclusive_sum(x) - x;
   }
   __syncthreads();
-#endif
-  auto emit_bucket = [&](uint32_t b, uint32_t c, uint32_t ni, uint32_t first, uint32_t slab, uint32_t mb) {
+  auto emit_bucket = [&](uint32_t b, uint32_t c, uint32_t ni, uint32_t slab, uint32_t mb) {
     if (b >= nb) return;
     o.bucket_count[b] = 0;
     o.b_items[b] = ni;
@@ -657,26 +643,20 @@ __device__ __forceinline__ uint32_t bk_plan_items(uint32_t c0, uint32_t c1, uint
     if (o.arrive) o.arrive[b] = 0;
     if (ni > lk) o.mlist[mb] = b;
     if (!ni) return;
-#if GS_BK_LPT
     const bool together = ni > 1 && ni <= inline_k;
     const uint32_t fpos = ni > 1 ? atomicAdd(&s_cls[size_class(item_recs)], together ? ni : ni - 1) : 0u;   // the full items
     const uint32_t lpos = together ? fpos + ni - 1 : atomicAdd(&s_cls[size_class(c - (ni - 1) * item_recs)], 1u);   // the last piece
-#endif
     for (uint32_t k = 0; k < ni; ++k) {
       BkItem it;
       it.bucket = b;
       it.begin = k * item_recs;   // relative; made absolute below
       it.end = min(c, (k + 1) * item_recs);
       it.slab = ni > 1 ? slab + k : ~0u;
-#if GS_BK_LPT
       o.items[k + 1 < ni ? fpos + k : lpos] = it;
-#else
-      o.items[first + k] = it;
-#endif
     }
   };
-  emit_bucket(b0, c0, i0, first0, slab0, mb0);
-  emit_bucket(b1, c1, i1, first0 + i0, slab0 + m0, mb0 + g0);
+  emit_bucket(b0, c0, i0, slab0, mb0);
+  emit_bucket(b1, c1, i1, slab0 + m0, mb0 + g0);
   if (o.max_items) {   // (s_maxit: zeroed before the item scans' barriers)
     if (i0 > 1 || i1 > 1) atomicMax(&s_maxit, max(i0, i1));
     __syncthreads();
@@ -776,16 +756,9 @@ static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_bk_plan(const uint32_t
 #ifndef GS_DP_ITEMS
 #define GS_DP_ITEMS 10
 #endif
-#ifndef GS_DP_XCD
-#define GS_DP_XCD 1
-#endif
-// 1: payloads go straight from registers to their global slot (off[t][b] + rank) instead of through
-// LDS; the tile's LDS drops to the staged keys + tables (two blocks per CU).  Measured on C2 (scatter,
-// ms): staged 10 items 1.65; direct 6 items 1.75 (staged 6 items 1.89); direct 8 and 10 items spill at
-// the 64-VGPR cap of two blocks per CU (2.20, 3.17).  Kept off; the A/B stays buildable.
-#ifndef GS_DP_VDIRECT
-#define GS_DP_VDIRECT 0
-#endif
+// The payloads are staged in LDS with the keys.  Payloads sent straight from registers to their global slot
+// (off[t][b] + rank; two blocks per CU) measured slower on C2 (scatter, ms): staged 10 items 1.65; direct 6
+// items 1.75 (staged 6 items 1.89); direct 8 and 10 items spill at the 64-VGPR cap (2.20, 3.17): removed.
 constexpr int DP_BLOCK = 1024;
 constexpr int DP_ITEMS = GS_DP_ITEMS;
 constexpr uint32_t DP_TILE = DP_BLOCK * DP_ITEMS;   // 10240 records < 2^16
@@ -992,22 +965,16 @@ __device__ __forceinline__ void dp_load_raw(const BaseSrc<V, DIR, PAY>& es, uint
 // per CU (1.71 ms), keys and values staged in turn through one region for 2 blocks per CU (1.81 ms
 // at 8192 records, 2.21 at 10240: the 64-VGPR cap spills).
 // V: loaded payload; VO: stored payload (REL: VO = V - base, out-of-range payloads set *rel_bad)
-#if GS_DP_VDIRECT
-#define GS_DP_SCATTER_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))   // two 16-wave blocks per CU
-#else
-#define GS_DP_SCATTER_ATTR
-#endif
 template <typename V, int DIR, int PAY, typename VO = V, bool REL = false>
-__global__ __launch_bounds__(DP_BLOCK) GS_DP_SCATTER_ATTR void k_dp_scatter(BaseSrc<V, DIR, PAY> es, uint64_t n, int S, uint32_t nbp,
+__global__ __launch_bounds__(DP_BLOCK) void k_dp_scatter(BaseSrc<V, DIR, PAY> es, uint64_t n, int S, uint32_t nbp,
                                                          const uint32_t* __restrict__ off,
                                                          uint16_t* __restrict__ k16, VO* __restrict__ vout,
                                                          uint32_t* __restrict__ rel_bad,
                                                          const unsigned long long* __restrict__ mm) {
   constexpr bool HAS_V = PAY != PAY_NONE;
   if (mm[2]) return;   // keys outside the predicted range: the window is rerun
-  constexpr bool STAGE_V = HAS_V && !GS_DP_VDIRECT;
   __shared__ uint32_t s_key[DP_TILE];                // (bucket << 16) | bucket-local index, bucket order
-  __shared__ VO s_val[STAGE_V ? DP_TILE : 1];
+  __shared__ VO s_val[HAS_V ? DP_TILE : 1];
   __shared__ uint32_t s_cnt[BK_MAXB];                // counts, then run starts inside the tile
   __shared__ uint32_t s_delta[BK_MAXB];              // global position - tile position of bucket b's run
   __shared__ uint32_t s_w[DP_BLOCK / WAVE];
@@ -1055,8 +1022,7 @@ __global__ __launch_bounds__(DP_BLOCK) GS_DP_SCATTER_ATTR void k_dp_scatter(Base
         } else if constexpr (HAS_V) {
           vo = vv[u];
         }
-        if constexpr (STAGE_V) s_val[pos] = vo;
-        else if constexpr (HAS_V) vout[s_delta[kb[u] >> 16] + pos] = vo;
+        if constexpr (HAS_V) s_val[pos] = vo;
       }
     }
     __syncthreads();
@@ -1067,14 +1033,14 @@ __global__ __launch_bounds__(DP_BLOCK) GS_DP_SCATTER_ATTR void k_dp_scatter(Base
         const uint32_t kv = s_key[j];
         const uint32_t d = s_delta[kv >> 16] + j;
         k16[d] = (uint16_t)kv;
-        if constexpr (STAGE_V) vout[d] = s_val[j];
+        if constexpr (HAS_V) vout[d] = s_val[j];
       }
     } else {
       for (uint32_t j = tid; j < nrec; j += DP_BLOCK) {
         const uint32_t kv = s_key[j];
         const uint32_t d = s_delta[kv >> 16] + j;
         k16[d] = (uint16_t)kv;
-        if constexpr (STAGE_V) vout[d] = s_val[j];
+        if constexpr (HAS_V) vout[d] = s_val[j];
       }
     }
   };
@@ -1093,12 +1059,8 @@ __global__ __launch_bounds__(DP_BLOCK) GS_DP_SCATTER_ATTR void k_dp_scatter(Base
   uint32_t ka[DP_ITEMS];
   V va[DP_ITEMS];
   {   // one full tile per block
-#if GS_DP_XCD
     const uint32_t per = (nfull + 7) / 8;
     const uint32_t t = blockIdx.x == gridDim.x - 1 ? nfull : (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-#else
-    const uint32_t t = blockIdx.x;
-#endif
     if (t < nfull) {
       uint32_t o0, o1;
       load_off(t, o0, o1);
@@ -1227,7 +1189,7 @@ void k_dp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
 // the scans computed: the window's keys are read once, not twice, and the per-tile count / offset
 // matrices (0.1 GB at C2) go away.  The reservation is issued before the tile's records go through LDS
 // and used after, so its latency hides behind the LDS scatter.  Each XCD slot reserves from its own
-// segment of the region (GS_SP_XCD): runs written at the same time by one XCD's blocks stay adjacent
+// segment of the region: runs written at the same time by one XCD's blocks stay adjacent
 // in one L2, and each cursor sees 1/8 of the atomics.  A run that would pass its segment's end is
 // written to a trash area instead, and a key outside the predicted range is dropped; both count in
 // mm[2], every later launch exits and the host reruns the window through k_dp_hist (which cannot
@@ -1332,12 +1294,6 @@ __host__ __device__ inline uint64_t sp_capacity(uint64_t r_now, uint32_t nb) {
 #ifndef GS_SPK_ITEMS
 #define GS_SPK_ITEMS 16
 #endif
-#ifndef GS_SPK_NT
-#define GS_SPK_NT 0
-#endif
-#ifndef GS_SPK_LATE
-#define GS_SPK_LATE 0   // 1: run deltas written after the LDS scatter (the reservations' latency hides behind it)
-#endif
 #ifndef GS_SPK_WAVES
 #define GS_SPK_WAVES 4   // waves per SIMD: one 1024-thread block or two 512-thread blocks per CU
 #endif
@@ -1376,14 +1332,8 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_w, u
 // The bucket a thread reserves (k of its BPT): k-major (tid + k * BLOCK), so one wave-instruction of
 // the reservation atomics covers 64 consecutive cursors -- 256 B, four 64-byte atomic transactions at the
 // memory side -- instead of 64 cursors two apart (eight transactions).  The run order inside a tile follows
-// the threads and is free (a run is contiguous either way).  A/B: GS_SPK_KMAJOR=0 (tid * BPT + k).
-#ifndef GS_SPK_VEC
-#define GS_SPK_VEC 1   // k_sp_scatter_pack: two records per lane and 16-byte column loads on full aligned tiles
-#endif
-#ifndef GS_SPK_KMAJOR
-#define GS_SPK_KMAJOR 1
-#endif
-#define SP_BK(k) (GS_SPK_KMAJOR ? (uint32_t)tid + (uint32_t)(k) * (uint32_t)BLOCK : (uint32_t)tid * BPT + (uint32_t)(k))
+// the threads and is free (a run is contiguous either way).
+#define SP_BK(k) ((uint32_t)tid + (uint32_t)(k) * (uint32_t)BLOCK)
 template <typename V, int DIR, int NB>
 __global__ __launch_bounds__(SPK_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_SPK_WAVES, GS_SPK_WAVES)))
 void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t nbp,
@@ -1395,14 +1345,8 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
   static_assert(NB <= BK_MAXB && (NB % BLOCK == 0 || NB < BLOCK), "bucket table shape");
   constexpr uint32_t TILE = SPK_TILE;
   constexpr uint32_t ESC = 1u << 31, DUMMY = (uint32_t)NB << 16;   // kb: escaped value / dummy bucket
-  __shared__ uint64_t s_slot[TILE];   // bucket order; early: packed << 32 | global position,
-                                      // late: packed << 32 | tile record << 12 | bucket
-#if GS_SPK_LATE
-  __shared__ uint32_t s_st[NB + 1];    // run starts in the tile
-  __shared__ uint32_t s_del[NB + 1];   // global start - tile start of each run
-#else
+  __shared__ uint64_t s_slot[TILE];   // bucket order: packed << 32 | global position
   __shared__ uint64_t s_run[NB + 1];   // global start of the run << 32 | its start in the tile
-#endif
   // per-bucket counts (the rank atomics): in the slots' space, read into registers before the scan's
   // barrier
   uint32_t* s_cnt = reinterpret_cast<uint32_t*>(s_slot);
@@ -1425,7 +1369,7 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
   }
   const uint32_t r0 = t * TILE;
   // this block's XCD slot: its segment (xmask 0: one segment per bucket, the merges' sorted runs)
-  const uint32_t xs = SP_NSEG == 1 ? 0u : blockIdx.x & xmask;
+  const uint32_t xs = blockIdx.x & xmask;
   auto col_index = [&](uint32_t j) -> uint32_t { return DIR == DIR_ALL ? (r0 + j) >> 1 : r0 + j; };
   // this thread's buckets (BPT consecutive ones): their segment ends, issued before the columns
   uint32_t send[BPT];
@@ -1433,13 +1377,12 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
   for (int k = 0; k < BPT; ++k) send[k] = cursor[SP_END_OFF + xs * BK_MAXB + min(SP_BK(k), nbp - 1)];
   cursor += xs * BK_MAXB;
   // loads: unconditional, clamped into the tile (k_dp_scatter).  Full OUT / IN tiles of 16-byte aligned
-  // columns (GS_SPK_VEC): two consecutive records per lane and load -- 16-byte key loads (and 16- or 8-byte
+  // columns: two consecutive records per lane and load -- 16-byte key loads (and 16- or 8-byte
   // value loads) instead of 8-byte ones, half the load instructions for the same bytes; record u of a
   // thread is then 2 ((u >> 1) BLOCK + tid) + (u & 1) of the tile (jof), which the ranking, the escapes and
   // the dead-lane check use -- the LDS slots and the stores do not depend on it.
   const int64_t* kcol = DIR == DIR_IN ? es.dst : es.src;
-  const bool vec = GS_SPK_VEC && DIR != DIR_ALL && nrec == TILE &&
-                   ((((uintptr_t)kcol) | ((uintptr_t)es.val)) & 15u) == 0;
+  const bool vec = DIR != DIR_ALL && nrec == TILE && ((((uintptr_t)kcol) | ((uintptr_t)es.val)) & 15u) == 0;
   auto jof = [&](int u) -> uint32_t {
     return vec ? 2u * ((uint32_t)(u >> 1) * BLOCK + tid) + (uint32_t)(u & 1) : (uint32_t)u * BLOCK + tid;
   };
@@ -1472,13 +1415,8 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
         i = r >> 1;
         rev = r & 1u;
       }
-#if GS_SPK_NT   // A/B: the columns are read once: non-temporal loads
-      kk[u] = __builtin_nontemporal_load(&(rev ? es.dst : es.src)[i]);
-      vv[u] = __builtin_nontemporal_load(&es.val[i]);
-#else
       kk[u] = (rev ? es.dst : es.src)[i];
       vv[u] = es.val[i];
-#endif
     }
   }
   for (uint32_t i = tid; i < nbp; i += BLOCK) s_cnt[i] = 0;
@@ -1515,46 +1453,7 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
   uint32_t st = block_excl_scan<BLOCK>(sum, s_w, total);   // total: records in the predicted range
   // A run that does not fit its segment goes to the trash area [trash, trash + TILE) past every region,
   // at its tile position (nothing reads the trash).
-#if GS_SPK_LATE
-  // late: the scatter needs only the tile starts; the reservations are waited for after it
-  uint32_t sb[BPT];
-#pragma unroll
-  for (int k = 0; k < BPT; ++k) {
-    sb[k] = st;
-    if (SP_BK(k) < NB) s_st[SP_BK(k)] = st;
-    st += cb[k];
-  }
-  if (tid == 0) s_st[NB] = total;   // the dummy run: the tile's last
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < ITEMS; ++u) {
-    const uint32_t b = (kb[u] >> 16) & 0x7FFFu;
-    const uint32_t packed = (kb[u] & 0xFFFFu) | (vr[u] & 0xFFFF0000u);
-    s_slot[s_st[b] + (vr[u] & 0xFFFFu)] = ((uint64_t)packed << 32) | (jof(u) << 12) | b;
-  }
-#pragma unroll
-  for (int k = 0; k < BPT; ++k) {
-    const bool drop = cb[k] && ob[k] + cb[k] > send[k];
-    ovf += drop ? 1u : 0u;
-    if (SP_BK(k) < NB) s_del[SP_BK(k)] = drop ? trash : ob[k] - sb[k];
-  }
-  if (tid == 0) s_del[NB] = trash;
-  __syncthreads();
-  uint32_t esc = 0;
-#pragma unroll
-  for (int u = 0; u < ITEMS; ++u) {
-    const uint32_t j = (uint32_t)u * BLOCK + tid;
-    const uint64_t e = s_slot[j];
-    const uint32_t g = j + s_del[(uint32_t)e & 0xFFFu];
-    const uint32_t packed = (uint32_t)(e >> 32);
-    rec[g] = packed;
-    if ((packed >> 16) == PK_ESC && ((uint32_t)e & 0xFFFu) != (uint32_t)NB) {   // rare: the full value into `wide`
-      wide[g] = es.val[col_index(((uint32_t)e >> 12) & 0xFFFFFu)];
-      ++esc;
-    }
-  }
-#else
-  // early: every slot carries its record's global position, so the store loop needs no table lookup
+  // Every slot carries its record's global position, so the store loop needs no table lookup
 #pragma unroll
   for (int k = 0; k < BPT; ++k) {
     const bool drop = cb[k] && ob[k] + cb[k] > send[k];
@@ -1591,7 +1490,6 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
     const uint64_t e = s_slot[(uint32_t)u * BLOCK + tid];
     rec[(uint32_t)e] = (uint32_t)(e >> 32);
   }
-#endif
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     esc += __shfl_xor(esc, o, WAVE);
@@ -1663,7 +1561,7 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     if (t >= nfull) return;
   }
   const uint32_t r0 = t * TILE;
-  const uint32_t xs = SP_NSEG == 1 ? 0u : blockIdx.x & xmask;
+  const uint32_t xs = blockIdx.x & xmask;
   uint32_t send[BPT];
 #pragma unroll
   for (int k = 0; k < BPT; ++k) send[k] = sp_hi(cursor, xs, min(SP_BK(k), nbp - 1));
@@ -1671,12 +1569,12 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
   int64_t kk[ITEMS];
   V vv[ITEMS];
   // full OUT / IN tiles of 16-byte aligned columns: two records per lane and load, as k_sp_scatter_pack
-  // (GS_SPK_VEC; record u of a thread is jof(u) of the tile, which only the dead-lane check uses)
+  // (record u of a thread is jof(u) of the tile, which only the dead-lane check uses)
   static_assert(ITEMS % 2 == 0, "two records per lane and load");
   const int64_t* kcol = DIR == DIR_IN ? es.dst : es.src;
   const void* pcol = PAY == PAY_VAL ? (const void*)es.val : PAY == PAY_NBR ? (const void*)(DIR == DIR_IN ? es.src : es.dst)
                                                                           : (const void*)kcol;
-  const bool vec = GS_SPK_VEC && DIR != DIR_ALL && nrec == TILE && ((((uintptr_t)kcol) | ((uintptr_t)pcol)) & 15u) == 0;
+  const bool vec = DIR != DIR_ALL && nrec == TILE && ((((uintptr_t)kcol) | ((uintptr_t)pcol)) & 15u) == 0;
   auto jof = [&](int u) -> uint32_t {
     return vec ? 2u * ((uint32_t)(u >> 1) * BLOCK + tid) + (uint32_t)(u & 1) : (uint32_t)u * BLOCK + tid;
   };
@@ -1732,7 +1630,7 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
   uint32_t rk[ITEMS];
 #pragma unroll
   for (int u = 0; u < ITEMS; ++u) {
-    if constexpr (GS_SP_MATCH && PAY == PAY_NBR) {
+    if constexpr (PAY == PAY_NBR) {
       // folds (C3's hub-heavy streams): the lanes sharing the wave's first lane's bucket take one atomic
       // for all of them instead of serialising same-address LDS atomics (Zipf C3 scatter 1.82 -> 1.44 ms;
       // R-MAT C3 +2 %, Double reduce +6 %: value reduces keep the plain atomics)
@@ -2219,8 +2117,8 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
     const uint32_t nrec = s_nrec[sl];   // (read here: not live across the stream)
     if (m.slab == ~0u) {
       // (an item without records: its bucket is empty, its count stays the plan's 0 and the table is untouched)
-      if (nrec) bk_finalize<P, GS_BK_FUSED_RESET != 0>(s, m.bucket, b0, st, bucket_count, s_wc);
-      reset = !nrec || GS_BK_FUSED_RESET != 0;
+      if (nrec) bk_finalize<P, true>(s, m.bucket, b0, st, bucket_count, s_wc);
+      reset = true;
     } else {
       // A bucket of 2 .. IK items is merged here: every item but the last to arrive dumps its table and then
       // takes a ticket on the bucket's arrival counter; the last adds the other slabs into its live table and
@@ -2286,8 +2184,8 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
           __syncthreads();
           bk_merge_slabs<P>(&s, slabs + f, ni, mine, empties);
           __syncthreads();
-          bk_finalize<P, GS_BK_FUSED_RESET != 0>(s, m.bucket, b0, st, bucket_count, s_wc);
-          reset = GS_BK_FUSED_RESET != 0;
+          bk_finalize<P, true>(s, m.bucket, b0, st, bucket_count, s_wc);
+          reset = true;
         }
       }
     }

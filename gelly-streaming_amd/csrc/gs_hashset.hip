@@ -369,12 +369,6 @@ __device__ __forceinline__ uint32_t cand_find_slot(const uint64_t* __restrict__ 
 // so the kernel holds fewer registers and more of its stores are in flight; every other step's base is
 // appended to `steps` (count in steps_n) for k_cand_emit_rest.  Kernels: k_cand_emit_all (MODE 0),
 // k_cand_emit_fast (MODE 1).
-#ifndef GS_CAND_LANE4
-#define GS_CAND_LANE4 1   // fast path: four consecutive positions per lane (A/B: 0 = positions strided by 64)
-#endif
-#ifndef GS_CAND_CARRY
-#define GS_CAND_CARRY 1   // fast path: a step after a fast step in the same slot starts from its row state (A/B: 0)
-#endif
 template <int MODE, typename OT>
 __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, uint32_t S,
                                                const CandMeta* __restrict__ meta, const int64_t* __restrict__ vkeys,
@@ -395,12 +389,10 @@ __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, 
   uint32_t cs = 0xFFFFFFFFu;
   uint64_t c_beg = 0, c_end = 0;
   CandMeta cm{};
-#if GS_CAND_LANE4 && GS_CAND_CARRY
   // the row state (row, its length, offset into it) of position k_next in slot k_slot: what the previous fast
   // step's last lane walked to, so a fast step that follows one in the same slot skips the closed-form row search
   uint32_t k_r = 0, k_len = 0, k_off = 0, k_slot = 0xFFFFFFFFu;
   uint64_t k_next = ~0ull;
-#endif
   for (uint64_t base = w0; base < w1; base += 256) {
     // Fast path: the step lies inside one slot's pair rows (most records of a window: the blocks of its
     // high-degree vertices are O(k^2)).  The slot's metadata is wave-uniform (scalar loads), the row of
@@ -420,16 +412,12 @@ __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, 
         const uint64_t k = m.k, rows = m.rows, q0 = t0 - m.d;
         const int64_t* G = gids + m.gbase;
         const uint32_t rows32 = (uint32_t)rows;
-#if GS_CAND_LANE4
         uint32_t r, len, off;
-#if GS_CAND_CARRY
         if (k_next == base && k_slot == sc) {
           r = k_r;
           len = k_len;
           off = k_off;
-        } else
-#endif
-        {
+        } else {
           const double k2 = 2.0 * (double)k + 1.0;
           uint64_t r0 = (uint64_t)fmax(0.0, (k2 - sqrt(fmax(0.0, k2 * k2 - 8.0 * (double)q0))) * 0.5);
           if (r0 >= rows) r0 = rows - 1;
@@ -458,13 +446,11 @@ __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, 
           av[j] = (OT)(G[r] - idb);
           bv[j] = (OT)(G[r + col] - idb);
         }
-#if GS_CAND_CARRY
         k_r = __shfl(r, 63, 64);   // the last lane's position is base + 255: one on is the next step's first
         k_len = __shfl(len, 63, 64);
         k_off = __shfl(off, 63, 64) + 1u;
         k_next = base + 256;
         k_slot = sc;
-#endif
         if ((f4 & 2) && o0 + 4 <= e1) {   // a and b 16-byte aligned; o0 - P0 is a multiple of 4
           if constexpr (sizeof(OT) == 4) {
             *reinterpret_cast<uint4*>(a + (o0 - P0)) = make_uint4(av[0], av[1], av[2], av[3]);
@@ -490,33 +476,6 @@ __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, 
           for (int j = 0; j < 4; ++j)
             if (o0 + j < e1) f[o0 + j - P0] = 1;
         }
-#else
-        const double k2 = 2.0 * (double)k + 1.0;
-        uint64_t r0 = (uint64_t)fmax(0.0, (k2 - sqrt(fmax(0.0, k2 * k2 - 8.0 * (double)q0))) * 0.5);
-        if (r0 >= rows) r0 = rows - 1;
-        for (int g = 0; g < 64 && r0 > 0 && tri_rows_before(r0, k) > q0; ++g) --r0;
-        for (int g = 0; g < 64 && r0 + 1 < rows && tri_rows_before(r0 + 1, k) <= q0; ++g) ++r0;
-        // a lane's positions increase with i, so its row walk carries over; it runs in 32 bits relative to
-        // the step's first row (row r holds k - r entries; off = q - rows_before(r) < k + 256), one add and
-        // compare per row crossed instead of two 64-bit row products per record
-        uint32_t r = (uint32_t)r0, len = (uint32_t)(k - r0);
-        uint32_t off = (uint32_t)(q0 - tri_rows_before(r0, k)) + lane;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (i) off += 64;
-          const uint64_t oi = base + (uint64_t)(i * 64) + lane;
-          if (oi >= e1) continue;
-          for (int g = 0; g < 64 && r + 1 < rows32 && off >= len; ++g) {
-            off -= len;
-            --len;
-            ++r;
-          }
-          const uint32_t col = min(off, len - 1);
-          a[oi - P0] = (OT)(G[r] - idb);
-          b[oi - P0] = (OT)(G[r + col] - idb);
-          if (!(f4 & 1)) f[oi - P0] = 1;
-        }
-#endif
         if (f4 & 1) {   // every flag of a pair row is 1: one 4-byte store per lane (256 B per wave) instead of four 64-B byte-store runs
           uint8_t* fr = f + (base - P0);   // base - P0 is a multiple of 256
           const uint64_t fo = 4ull * lane;
@@ -554,16 +513,8 @@ __device__ __forceinline__ void cand_emit_body(const uint64_t* __restrict__ vs, 
 #define GS_CAND_EMIT_PASS vs, S, meta, vkeys, nbr, gids, P0, P1, per_wave, a, b, f, f4, steps, steps_n, idb
 template <typename OT>
 __global__ __launch_bounds__(256) void k_cand_emit_all(GS_CAND_EMIT_ARGS) { cand_emit_body<0, OT>(GS_CAND_EMIT_PASS); }
-#ifndef GS_CAND_FAST_WAVES
-#define GS_CAND_FAST_WAVES 0   // A/B: a waves-per-SIMD target for k_cand_emit_fast (0 = the compiler's choice)
-#endif
-#if GS_CAND_FAST_WAVES
-#define GS_CAND_FAST_ATTR __attribute__((amdgpu_waves_per_eu(GS_CAND_FAST_WAVES)))
-#else
-#define GS_CAND_FAST_ATTR
-#endif
 template <typename OT>
-__global__ __launch_bounds__(256) GS_CAND_FAST_ATTR void k_cand_emit_fast(GS_CAND_EMIT_ARGS) {
+__global__ __launch_bounds__(256) void k_cand_emit_fast(GS_CAND_EMIT_ARGS) {
   cand_emit_body<1, OT>(GS_CAND_EMIT_PASS);
 }
 

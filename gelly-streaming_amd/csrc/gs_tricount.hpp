@@ -38,17 +38,11 @@ constexpr int TH_HBLOCK = GS_TH_HBLOCK;
 #define GS_TH_VCH 1024
 #endif
 constexpr uint32_t TH_NU = GS_TH_NU, TH_HB = TH_NU / 2, TH_VCH = GS_TH_VCH;   // TH_HB 4-slot buckets: load <= 1/2
-#ifndef GS_TH_BITMAP
-#define GS_TH_BITMAP 1   // k_tri_heavy: N+(v) as a bitmap over (v, last] when the span fits the table
-#endif
-constexpr bool TH_BITMAP = GS_TH_BITMAP;
+// k_tri_heavy keeps N+(v) as a bitmap over (v, last] when the span fits the table (a wave's table in k_tri_light
+// measured slower: light count s24 7.08 vs 6.92 ms hash, removed).
 // the heavy table's bits (TH_HB 16-byte buckets) less one word: the bitmap of a span of up to TH_BSPAN bits
 // keeps a zero word after its last, which items past the span index (k_tri_heavy's branch-free probe)
 constexpr uint32_t TH_BSPAN = TH_NU / 2 * 128u - 32u;
-#ifndef GS_TH_LBITMAP
-#define GS_TH_LBITMAP 0  // k_tri_light: the same for a wave's table (spans up to TH_H·32 bits); A/B: light count s24 7.08 vs 6.92 ms hash, off
-#endif
-constexpr bool TH_LBITMAP = GS_TH_LBITMAP;
 static_assert(TH_VCH % TH_HBLOCK == 0, "TH_VCH must be a multiple of TH_HBLOCK");
 #ifndef GS_TH_DMAX
 #define GS_TH_DMAX 512   // light capacity (out-list of a light vertex, in-entries per light chunk); with the heavy bitmaps: s26 455 -> 376 ms
@@ -79,19 +73,9 @@ constexpr uint32_t TH_LONG = GS_TH_LONG;
 #ifndef GS_TH_LWAVES
 #define GS_TH_LWAVES 6   // k_tri_light waves per SIMD the registers are capped for (4 -> 6: s22 3.03 -> 2.38 ms)
 #endif
-#ifndef GS_TH_WALK
-#define GS_TH_WALK 1     // k_tri_heavy: branch-free list walk (A/B, s26 heavy 144.5 -> 140.7 ms; 0 = a branch and an
-                         // LDS round trip per item, in series)
-#endif
-#ifndef GS_TH_LWALK
-#define GS_TH_LWALK 0    // k_tri_light: the same (A/B: light 39.6 -> 40.2 ms at s26, not kept)
-#endif
-#ifndef GS_TH_LPIPE
-#define GS_TH_LPIPE 0    // k_tri_light: the same (A/B)
-#endif
-#ifndef GS_TH_PIPE
-#define GS_TH_PIPE 0     // k_tri_heavy: gathers of the next step issued before this step's probes (A/B)
-#endif
+// k_tri_heavy walks its short lists branch-free (s26 heavy 144.5 -> 140.7 ms against a branch and an LDS round
+// trip per item, in series); the same walk in k_tri_light measured slower (light 39.6 -> 40.2 ms at s26) and
+// is not there.
 #ifndef GS_TH_HWAVES
 #define GS_TH_HWAVES 6   // k_tri_heavy: three 512-thread blocks per CU (4 -> 6: s22 11.4 -> 9.8 ms, s24 72.3 -> 62.5)
 #endif
@@ -172,36 +156,15 @@ __device__ __forceinline__ uint32_t th_probe(const uint4* hb, uint32_t bmask, co
   return cnt;
 }
 
-// cnt += probe(items of step k0) for k0 = a, a + step, .. < b, the items from gather(k0, x) -> valid count.
-// PIPE: software-pipelined -- step k0 + step's gathers (and the list search that places them) issue before
-// step k0's probes, so the search's LDS chain and the gathers' memory latency of consecutive steps overlap
+// cnt += probe(items of step k0) for k0 = a, a + step, .. < b, the items from gather(k0, x) -> valid count
 // (the loop bound is uniform over the caller's wave or block)
-template <int PIPE, class C, class Gather, class Probe>
-__device__ __forceinline__ void th_pipelined(uint32_t a, uint32_t b, uint32_t step, Gather&& gather, Probe&& probe,
-                                             C& cnt) {
-  if constexpr (PIPE) {
-    if (a >= b) return;
-    uint32_t xa[TH_ILP];
-    uint32_t nva = gather(a, xa);
-    for (uint32_t k0 = a; k0 < b; k0 += step) {
-      uint32_t xb[TH_ILP], nvb = 0;
-      if (k0 + step < b) {
-        nvb = gather(k0 + step, xb);
-      } else {
-#pragma unroll
-        for (int j = 0; j < TH_ILP; ++j) xb[j] = 0u;
-      }
-      cnt += probe(xa, nva);
-#pragma unroll
-      for (int j = 0; j < TH_ILP; ++j) xa[j] = xb[j];
-      nva = nvb;
-    }
-  } else {
-    for (uint32_t k0 = a; k0 < b; k0 += step) {
-      uint32_t x[TH_ILP];
-      const uint32_t nv = gather(k0, x);
-      cnt += probe(x, nv);
-    }
+template <class C, class Gather, class Probe>
+__device__ __forceinline__ void th_probe_steps(uint32_t a, uint32_t b, uint32_t step, Gather&& gather, Probe&& probe,
+                                               C& cnt) {
+  for (uint32_t k0 = a; k0 < b; k0 += step) {
+    uint32_t x[TH_ILP];
+    const uint32_t nv = gather(k0, x);
+    cnt += probe(x, nv);
   }
 }
 
@@ -230,7 +193,7 @@ __device__ __forceinline__ uint32_t th_wave_probe(const uint32_t* __restrict__ o
     if (sh) {
       const uint32_t at = dn + mbcnt(ms);
       po[at] = run + inc - ds;
-      ps[at] = GS_TH_LWALK ? su - (run + inc - ds) : su;   // (walk: item k of list at is onbr[k + ps[at]])
+      ps[at] = su;
     }
     if (lg) {
       const uint32_t at = CAP - 1 - (nl + mbcnt(ml));
@@ -267,7 +230,7 @@ __device__ __forceinline__ uint32_t th_wave_probe(const uint32_t* __restrict__ o
       const uint32_t rem = lrun - k0;
       return rem > (uint32_t)lane ? min((uint32_t)TH_ILP, (rem - lane + WAVE - 1) / WAVE) : 0u;
     };
-    th_pipelined<GS_TH_LPIPE>(0u, lrun, (uint32_t)(WAVE * TH_ILP), gather_long, probe, cnt);
+    th_probe_steps(0u, lrun, (uint32_t)(WAVE * TH_ILP), gather_long, probe, cnt);
   }
   uint32_t top = 1;
   while (2 * top < dn) top <<= 1;
@@ -281,22 +244,6 @@ __device__ __forceinline__ uint32_t th_wave_probe(const uint32_t* __restrict__ o
       const uint32_t pv = t < dn ? po[min(t, dn - 1)] : run;
       lo = pv <= kk ? t : lo;
     }
-#if GS_TH_LWALK
-    // branch-free, as k_tri_heavy's walk: the next TH_ILP - 1 list starts as a mask of the items that start one
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 1; i < TH_ILP; ++i) {
-      const uint32_t t = lo + (uint32_t)i;
-      const uint32_t d = (t < dn ? po[min(t, dn - 1)] : run) - kb;
-      m |= d < (uint32_t)TH_ILP ? 1u << d : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < TH_ILP; ++j) {
-      const uint32_t ql = min(lo + (uint32_t)__builtin_popcount(m & ((2u << j) - 1u)), dn - 1);
-      x[j] = onbr[min(kb + j, run - 1) + ps[ql]];
-    }
-    return kb < run ? min((uint32_t)TH_ILP, run - kb) : 0u;
-#endif
     // consecutive items cross at most one list boundary per step (every kept list has >= 1 item)
     uint32_t o = po[lo], st = ps[lo], q = lo;
     uint32_t nx = q + 1 < dn ? po[min(q + 1, dn - 1)] : run;
@@ -313,42 +260,18 @@ __device__ __forceinline__ uint32_t th_wave_probe(const uint32_t* __restrict__ o
     }
     return kb < run ? min((uint32_t)TH_ILP, run - kb) : 0u;
   };
-  th_pipelined<GS_TH_LPIPE>(0u, run, (uint32_t)(WAVE * TH_ILP), gather_short, probe, cnt);
+  th_probe_steps(0u, run, (uint32_t)(WAVE * TH_ILP), gather_short, probe, cnt);
   wave_lds_sync();   // po / ps are reused by the next chunk
   return cnt;
 }
 
 // one wave: N+(v) into the wave's own LDS hash set, then the in-entries c0 .. c1 (<= TH_LCH) of v
 __device__ __forceinline__ uint32_t th_wave_chunk(const uint32_t* __restrict__ onbr, const uint2* __restrict__ sfx,
-                                                  uint32_t v_id, uint2 ro, uint32_t c0,
-                                                  uint32_t c1, int lane, uint4* hb, uint32_t* po, uint32_t* ps,
-                                                  uint64_t& probes, uint32_t nb_cap, uint32_t* err) {
+                                                  uint2 ro, uint32_t c0, uint32_t c1, int lane, uint4* hb,
+                                                  uint32_t* po, uint32_t* ps, uint64_t& probes, uint32_t nb_cap,
+                                                  uint32_t* err) {
   uint32_t* hs = reinterpret_cast<uint32_t*>(hb);
   const uint32_t d = ro.y - ro.x;
-  // a bitmap over (v, last] when the span fits the table's TH_H·32 bits (k_tri_heavy): the high-rank
-  // light vertices (hubs with few higher neighbours)
-  const uint32_t v = uni(v_id), span = uni(onbr[ro.y - 1] - v);
-  if (TH_LBITMAP && nb_cap > 1 && span <= TH_H * 32u) {
-    const uint32_t nw = (span + 31) / 32;
-    for (uint32_t i = lane; i < nw; i += WAVE) hs[i] = 0u;
-    wave_lds_sync();
-    for (uint32_t i = lane; i < d; i += WAVE) {
-      const uint32_t o = onbr[ro.x + i] - v - 1;
-      atomicOr(&hs[o >> 5], 1u << (o & 31));
-    }
-    wave_lds_sync();
-    return th_wave_probe<TH_LCH>(onbr, sfx, c0, c1, lane, po, ps, probes,
-                                  [&](const uint32_t (&x)[TH_ILP], uint32_t nv) {
-                                    uint32_t c = 0;
-#pragma unroll
-                                    for (int j = 0; j < TH_ILP; ++j) {
-                                      const uint32_t o = x[j] - v - 1;
-                                      const uint32_t wv = hs[min(o, span - 1) >> 5];
-                                      c += ((uint32_t)j < nv && o < span) ? (wv >> (o & 31)) & 1u : 0u;
-                                    }
-                                    return c;
-                                  });
-  }
   uint32_t nb = 16;
   while (nb < d && nb < TH_H / 4) nb <<= 1;
   nb = min(nb, nb_cap);
@@ -387,7 +310,7 @@ __global__ __launch_bounds__(TH_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH_
     const uint32_t v = q.x;
     const uint2 ri = in_range[v];
     const uint32_t c0 = ri.x + q.y * TH_LCH, c1 = min(ri.y, c0 + TH_LCH);
-    cnt += th_wave_chunk(onbr, sfx, v, out_range[v], c0, c1, lane, s_hash[w], s_off[w], s_st[w], probes,
+    cnt += th_wave_chunk(onbr, sfx, out_range[v], c0, c1, lane, s_hash[w], s_off[w], s_st[w], probes,
                          nb_cap, err);
   }
 #pragma unroll
@@ -431,7 +354,7 @@ __global__ __launch_bounds__(TH_LCBLOCK) void k_tri_lclass(const uint32_t* __res
       if (ro.y != ro.x && ri.y != ri.x && ro.x >= q0 && ro.x < q1) {
         const uint32_t dv = ro.y - ro.x;
         const bool heavy_v = dv > TH_DMAX ||
-                             (TH_BITMAP && nb_cap > 1 && dv > TH_HMIN && onbr[ro.y - 1] - v <= TH_BSPAN);
+                             (nb_cap > 1 && dv > TH_HMIN && onbr[ro.y - 1] - v <= TH_BSPAN);
         if (heavy_v) nh = (ri.y - ri.x + TH_VCH - 1) / TH_VCH;
         else nl = (ri.y - ri.x + TH_LCH - 1) / TH_LCH;
       }
@@ -638,7 +561,7 @@ __global__ __launch_bounds__(TH_HBLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH
     // the table a binary search in HBM.  Degree-class ranks put every heavy vertex near the top of the
     // order, so the span is short (R-MAT s22: < 2^16 for all of the heavy work).
     const uint32_t span = uni(d ? onbr[ro.y - 1] - v : 0u);
-    const bool bitmap = TH_BITMAP && span <= TH_BSPAN && nb_cap > 1;   // (tiny test tables: hash only)
+    const bool bitmap = span <= TH_BSPAN && nb_cap > 1;   // (tiny test tables: hash only)
     const bool in_lds = bitmap || d <= TH_NU;
     uint32_t nb = 16;
     while (nb * 2 < d && nb < TH_HB) nb <<= 1;
@@ -732,7 +655,7 @@ __global__ __launch_bounds__(TH_HBLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH
         lo_ += du[j];
       } else if (du[j]) {
         s_off[si] = so;
-        s_st[si] = GS_TH_WALK ? su[j] - so : su[j];   // (walk: item k of list si is onbr[k + s_st[si]])
+        s_st[si] = su[j] - so;   // (item k of list si is onbr[k + s_st[si]])
         ++si;
         so += du[j];
       }
@@ -755,7 +678,6 @@ __global__ __launch_bounds__(TH_HBLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH
         const uint32_t t = q + st;
         q = (t < ns && s_off[min(t, ns - 1)] <= kk) ? t : q;
       }
-#if GS_TH_WALK
       // (round 6) branch-free: the next TH_ILP - 1 list starts in one batch of LDS reads, as a mask of the
       // items that start a list (s_off[ns] = srun lies past every item); item j lies in list q + (starts at
       // or before j), whose base is one more batch of reads -- instead of a branch and an LDS round trip
@@ -772,22 +694,9 @@ __global__ __launch_bounds__(TH_HBLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH
         x[j] = onbr[min(kb + j, srun - 1) + s_st[ql]];
       }
       return kb < srun ? min((uint32_t)TH_ILP, srun - kb) : 0u;
-#endif
-      uint32_t nx = s_off[q + 1], base = s_st[q] - s_off[q];   // item kj of list q: onbr[kj + base]
-#pragma unroll
-      for (int j = 0; j < TH_ILP; ++j) {
-        const uint32_t kj = min(kb + j, srun - 1);
-        if (kj >= nx) {
-          ++q;
-          base = s_st[q] - nx;
-          nx = s_off[q + 1];
-        }
-        x[j] = onbr[kj + base];
-      }
-      return kb < srun ? min((uint32_t)TH_ILP, srun - kb) : 0u;
     };
     constexpr uint32_t SSTEP = TH_HBLOCK * TH_ILP, LSTEP = WAVE * TH_ILP;
-    th_pipelined<GS_TH_PIPE>(0u, srun, SSTEP, gather_short, probe, cnt);
+    th_probe_steps(0u, srun, SSTEP, gather_short, probe, cnt);
     // long lists: wave w walks items [w, w + 1) * lrun / NW in 64-item segments (one load of 64
     // consecutive items); a segment spans at most two lists (every long list >= 64 items)
     if (lrun) {
@@ -822,7 +731,7 @@ __global__ __launch_bounds__(TH_HBLOCK) __attribute__((amdgpu_waves_per_eu(GS_TH
         const uint32_t rem = a1 - k0;
         return rem > (uint32_t)lane ? min((uint32_t)TH_ILP, (rem - lane + WAVE - 1) / WAVE) : 0u;
       };
-      th_pipelined<GS_TH_PIPE>(a0, a1, LSTEP, gather_long, probe, cnt);
+      th_probe_steps(a0, a1, LSTEP, gather_long, probe, cnt);
     }
   }
 #pragma unroll

@@ -160,8 +160,8 @@ def test_reduce_unaligned_device_slices(engine, oracle):
 
 def test_speculative_window_unaligned_device_slices(engine, oracle):
     """The speculative scatter reads two records per lane with 16-byte loads only from 16-byte aligned
-    columns (k_sp_scatter_pack, GS_SPK_VEC): a second window of the same geometry (it speculates) over views
-    at an odd offset -- keys only, values only, both -- takes the 8-byte path and gives the same output."""
+    columns (the `vec` path of k_sp_scatter_pack): a second window of the same geometry (it speculates) over
+    views at an odd offset -- keys only, values only, both -- takes the 8-byte path and gives the same output."""
     n = 1 << 18
     s, d = oracle.gen_rmat(16, n + 2, 79)
     v = oracle.gen_values(n + 2, 80, oracle.DT_I64)
