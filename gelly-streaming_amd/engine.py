@@ -472,11 +472,19 @@ class Engine:
             ptr, nbytes = (buf.ctypes.data if buf.size else None), buf.size
         in_mem = L.GS_MEM_DEVICE if dev_in else L.GS_MEM_HOST
         n_out, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        cap = nbytes // 6 + 1          # a record takes at least 6 bytes ("0 0 0\n"), the last one 5
-        cols = [self._empty(out_device, cap, np.int64) for _ in range(3)]
-        self._check(self._L.gs_parse_edges_text(self.ctx, ptr, nbytes, in_mem, _ptr(cols[0]), _ptr(cols[1]),
-                                                _ptr(cols[2]), cap, L.GS_MEM_DEVICE if out_device else L.GS_MEM_HOST,
-                                                ctypes.pointer(n_out), ctypes.pointer(bad)))
+        # a well-formed record takes at least 6 bytes ("0 0 0\n"), the last one 5; a text with more
+        # records than that holds a malformed one (an empty line is a record of one byte), and the
+        # second call with the count the first one returned lets the library name it
+        cap = nbytes // 6 + 1
+        while True:
+            cols = [self._empty(out_device, cap, np.int64) for _ in range(3)]
+            st = self._L.gs_parse_edges_text(self.ctx, ptr, nbytes, in_mem, _ptr(cols[0]), _ptr(cols[1]),
+                                             _ptr(cols[2]), cap, L.GS_MEM_DEVICE if out_device else L.GS_MEM_HOST,
+                                             ctypes.pointer(n_out), ctypes.pointer(bad))
+            if st != L.GS_ECAPACITY or n_out.value <= cap:
+                break
+            cap = n_out.value
+        self._check(st)
         n = n_out.value
         return tuple(c[:n] for c in cols)
 

@@ -560,7 +560,9 @@ GS_API gs_status gs_window_count_candidates(gs_ctx* ctx, const gs_pair_batch* pa
  * char; fields after the third are ignored.  Outputs src, dst, ts (the edge value the example turns
  * into the event time) in record order.  Two-phase: *n_out = records (GS_ECAPACITY when capacity is
  * short).  A record where the reference's map would throw gives GS_EINVAL and its index in
- * *bad_record (~0 otherwise).  text < 4 GiB per call. */
+ * *bad_record (~0 otherwise).  text < 4 GiB per call.  Only the ASCII digits '0'..'9' are accepted:
+ * Long.parseLong goes through Character.digit and would also take other Unicode decimal digits
+ * (e.g. U+0661), which are malformed here; this is a documented limit. */
 GS_API gs_status gs_parse_edges_text(gs_ctx* ctx, const char* text, uint64_t bytes, int32_t in_mem, int64_t* src,
                                      int64_t* dst, int64_t* ts, uint64_t capacity, int32_t out_mem,
                                      uint64_t* n_out, uint64_t* bad_record);
