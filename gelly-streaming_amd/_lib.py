@@ -25,6 +25,7 @@ GS_TIMING_OFF, GS_TIMING_DOMINANT, GS_TIMING_STAGES = 0, 1, 2   # gs_set_timing
 GS_READBACK_STREAM, GS_READBACK_EARLY, GS_READBACK_EARLY_TIMEOUT = 0, 1, 2   # gs_last_readback
 GS_I32, GS_I64, GS_F32, GS_F64, GS_NONE = 0, 1, 2, 3, 4
 GS_OP_SUM, GS_OP_MIN, GS_OP_MAX, GS_OP_COUNT = 0, 1, 2, 3
+GS_DISTINCT_KEYED, GS_DISTINCT_INSTANCE = 0, 1   # gs_distinct_mode
 STATUS_NAMES = {0: "GS_OK", -1: "GS_EINVAL", -2: "GS_ECAPACITY", -3: "GS_EDEVICE", -4: "GS_ECOMM",
                 -5: "GS_ENOMEM", -6: "GS_EUNSUPPORTED", -7: "GS_EAGAIN"}
 
@@ -49,7 +50,9 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_stream_poll", "gs_stream_stats", "gs_generate_rmat", "gs_generate_uniform", "gs_generate_zipf", "gs_generate_values", "gs_last_stage_times", "gs_last_readback",
            "gs_set_max_window_records", "gs_candidates_begin", "gs_candidates_begin_part", "gs_candidates_next", "gs_candidates_next_u32", "gs_candidates_seek",
            "gs_candidates_vertex_range", "gs_cont_create", "gs_cont_destroy", "gs_cont_size", "gs_cont_capacity",
-           "gs_cont_degrees", "gs_cont_vertices", "gs_cont_export", "gs_cont_import")
+           "gs_cont_degrees", "gs_cont_vertices", "gs_cont_export", "gs_cont_import",
+           "gs_distinct_create", "gs_distinct_destroy", "gs_distinct_edges", "gs_distinct_size", "gs_distinct_capacity",
+           "gs_distinct_export", "gs_distinct_import")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -77,6 +80,11 @@ class GsEdgeBatch(ctypes.Structure):
 class GsVertexOut(ctypes.Structure):
     _fields_ = [("keys", P), ("vals", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)), ("mem", i32),
                 ("reserved", i32)]
+
+
+class GsEdgeOut(ctypes.Structure):   # gs_edge_out: the edges gs_distinct_edges / _export emit
+    _fields_ = [("src", P), ("dst", P), ("val", P), ("index", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)),
+                ("mem", i32), ("reserved", i32)]
 
 
 class GsDegreeOut(ctypes.Structure):
@@ -259,6 +267,13 @@ def load() -> ctypes.CDLL:
         "gs_cont_vertices": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsVertexOut)]),
         "gs_cont_export": (st, [P, P, ctypes.POINTER(GsVertexOut)]),
         "gs_cont_import": (st, [P, P, ctypes.POINTER(GsPartialBatch)]),
+        "gs_distinct_create": (st, [P, i32, u64, ctypes.POINTER(P)]),
+        "gs_distinct_destroy": (None, [P]),
+        "gs_distinct_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsEdgeOut)]),
+        "gs_distinct_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_distinct_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_distinct_export": (st, [P, P, ctypes.POINTER(GsEdgeOut)]),
+        "gs_distinct_import": (st, [P, P, ctypes.POINTER(GsEdgeBatch)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)

@@ -41,15 +41,6 @@ struct CtTable {
   unsigned long long* meta;
 };
 
-__device__ __forceinline__ unsigned long long ct_hash(unsigned long long x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-
 // the slot of `id` (!= CT_EMPTY), claimed if absent (*fresh); ~0 when the table is full (not reached at
 // load <= 1/2).  A slot read as another id stays that id for good, so only an EMPTY read needs the CAS.
 __device__ __forceinline__ unsigned long long ct_slot(const CtTable& t, unsigned long long id, bool* fresh) {

@@ -103,7 +103,8 @@ struct gs_ctx {
   gs::DevBuf tri_loops, tri_tiles, tri_sfx, tri_nbr, tri_heavy, tri_range, tri_queue, tri_hwork;
   gs::DevBuf tri_d[10];          // split-window triangles (gs_window_triangles_dist)
   gs::DevBuf cc[4];              // connected components (gs_components.hip; [3]: the giant tree's bits)
-  gs::DevBuf ct[5];              // continuous streams (gs_continuous.hip): run keys, offsets, bases, flags, scan
+  gs::DevBuf ct[5];              // continuous streams (gs_continuous.hip): run keys, offsets, bases, flags, scan;
+                                 // gs_distinct.hip: [0] held slots, [3] keep flags, [4] their scan
   uint32_t tri_guess_B = 0;      // triangles: the previous window's id width (its partition histograms ride the id scan)
   uint32_t tri_B = 0;            // split-window triangles: id geometry of the current window
   uint64_t tri_key_xor = 0;

@@ -27,6 +27,16 @@ __host__ __device__ inline uint32_t owner_of(int64_t v, uint32_t nparts) {
   return (uint32_t)(((x >> 32) * (uint64_t)nparts) >> 32);
 }
 
+// the murmur3 finaliser: the slot hash of the device-resident tables (gs_continuous.hip, gs_distinct.hip)
+__device__ __forceinline__ unsigned long long ct_hash(unsigned long long x) {
+  x ^= x >> 33;
+  x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33;
+  x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+
 // one block: exclusive scan of cnt[0 .. n) (owner-major) in place; totals[o] = partials of owner o, *n_out
 // (optional) = all of them (gs_dist.hip's owner partition; the bucket path's owner-grouped emit)
 static __global__ __launch_bounds__(1024) void k_owner_scan(uint32_t* __restrict__ cnt, uint32_t n, uint32_t tiles,

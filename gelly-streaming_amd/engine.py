@@ -686,6 +686,12 @@ class Engine:
         (getDegrees / getInDegrees / getOutDegrees / getVertices / numberOfVertices): one per operator."""
         return ContinuousState(self, reserve_vertices)
 
+    def distinct(self, mode: str = "keyed", reserve_edges: int = 0) -> "DistinctState":
+        """gs_distinct_create: an empty device-resident edge set for SimpleEdgeStream.distinct().  mode "keyed":
+        an edge passes iff its (src, dst) pair is new; "instance": iff its dst is new (the literal
+        DistinctEdgeMapper at parallelism 1).  reserve_edges: the distinct edges expected plus one batch."""
+        return DistinctState(self, mode, reserve_edges)
+
     # -- multi-GPU keyBy halves (gs_dist.hip) --------------------------------------------------------
     def reduce_partials(self, src, dst, val, direction, op, nparts: int):
         """gs_window_reduce_partials: this slice's per-vertex partials grouped by owner (gs_owner_of).
@@ -968,3 +974,94 @@ class ContinuousState:
             counts = np.ascontiguousarray(counts, dtype=np.int64)
         pb, keep, dev = self.engine._partial_batch(keys, counts)
         self.engine._check(self._L.gs_cont_import(self.engine.ctx, self.handle, ctypes.byref(pb)))
+
+
+class DistinctState:
+    """gs_distinct: the state of one SimpleEdgeStream.distinct() (include/gelly_hip.h, "distinct()") -- a hash
+    set of the edges seen so far and their log in first-arrival order, in HBM across calls.  Feed it the stream
+    in batches of any size: the concatenated outputs depend only on the stream.  Columns are numpy arrays
+    (results come back as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
+
+    MODES = {"keyed": L.GS_DISTINCT_KEYED, "instance": L.GS_DISTINCT_INSTANCE}
+
+    def __init__(self, engine: Engine, mode: str = "keyed", reserve_edges: int = 0):
+        if mode not in self.MODES:
+            raise ValueError(f"mode: one of {sorted(self.MODES)}")
+        self.engine = engine
+        self.mode = mode
+        self._L = engine._L
+        h = ctypes.c_void_p()
+        engine._check(self._L.gs_distinct_create(engine.ctx, self.MODES[mode], int(reserve_edges), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.gs_distinct_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def edges(self, src, dst, val=None, out=None):
+        """gs_distinct_edges: the edges of the batch never seen before, in arrival order, as (src, dst, val,
+        index) -- val the first arrivals' values bit for bit (None without a value column), index their
+        positions inside the batch.  out: optional (src, dst, val, index) device tensors of at least the
+        batch's edges (int64 ids and index, val of the batch's dtype or None), reused across batches."""
+        e = self.engine
+        b, keep, dev = e._batch(src, dst, val)
+        n = b.n
+        vdt = None if val is None else L.NP_DTYPE[b.val_dtype]
+        if out is not None:
+            if len(out) != 4 or (out[2] is None) != (val is None):
+                raise ValueError("out: (src, dst, val, index), val None exactly when the batch has no values")
+            e._check_out([t for t in out if t is not None], dev, (np.int64, np.int64) + ((vdt,) if vdt else ()) + (np.int64,), n)
+            os_, od, ov, oi = out
+        else:
+            os_, od, oi = (e._empty(dev, n, np.int64) for _ in range(3))
+            ov = None if vdt is None else e._empty(dev, n, vdt)
+        n_out = ctypes.c_uint64(0)
+        eo = L.GsEdgeOut(_ptr(os_), _ptr(od), _ptr(ov), _ptr(oi), n, ctypes.pointer(n_out),
+                         L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_distinct_edges(e.ctx, self.handle, ctypes.byref(b), ctypes.byref(eo)))
+        k = n_out.value
+        return os_[:k], od[:k], None if ov is None else ov[:k], oi[:k]
+
+    def size(self):
+        """gs_distinct_size: (distinct edges kept, records seen, duplicates included)."""
+        d, r = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_distinct_size(self.handle, ctypes.byref(d), ctypes.byref(r)))
+        return d.value, r.value
+
+    def capacity(self):
+        """gs_distinct_capacity: (slots of the table, doublings so far); load factor = size()[0] / slots."""
+        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_distinct_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
+        return s.value, g.value
+
+    def export(self, device: bool = False):
+        """gs_distinct_export: the checkpoint -- (src, dst) of the distinct edges in first-arrival order (the
+        operator's output so far), numpy or (device=True) CUDA tensors."""
+        e = self.engine
+        D = self.size()[0]
+        src, dst = e._empty(device, D, np.int64), e._empty(device, D, np.int64)
+        n_out = ctypes.c_uint64(0)
+        eo = L.GsEdgeOut(_ptr(src), _ptr(dst), None, None, D, ctypes.pointer(n_out),
+                         L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_distinct_export(e.ctx, self.handle, ctypes.byref(eo)))
+        n = n_out.value
+        return src[:n], dst[:n]
+
+    def load(self, src, dst):
+        """gs_distinct_import: restore a checkpoint into this, still empty, state (rows in any order, a repeated
+        row taken once)."""
+        b, keep, dev = self.engine._batch(src, dst, None)
+        self.engine._check(self._L.gs_distinct_import(self.engine.ctx, self.handle, ctypes.byref(b)))

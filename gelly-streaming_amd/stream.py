@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's windowed graph-stream API, backed by libgellyhip.so.
 
   SimpleEdgeStream   <- streaming/SimpleEdgeStream.java:59-540 (constructors :73-94, slice :139-171,
-                        reverse :332-341, undirected :354-365; the continuous operators getVertices :119-125,
+                        distinct :305-327, reverse :332-341, undirected :354-365; the continuous operators
+                        getVertices :119-125,
                         numberOfVertices :370-387, numberOfEdges :392-408, getDegrees / getInDegrees /
                         getOutDegrees :416-442)
   GraphWindowStream  <- streaming/GraphWindowStream.java:47-183 (foldNeighbors :62, reduceOnEdges :101,
@@ -301,6 +302,40 @@ class SimpleEdgeStream:
             out.windows.append(WindowOutput(0, 0, ("records", list(range(seen + 1, seen + len(src) + 1)))))
             seen += len(src)
         return out
+
+    def distinct(self, per_vertex: bool = True) -> "SimpleEdgeStream":
+        """:305-327 -> the stream without its repeated edges: each edge at its first arrival, unchanged (value
+        and timestamp), in arrival order.  The stream goes through one fresh device state in
+        env.getMicroBatch()-sized batches; the result does not depend on that size.
+
+        per_vertex=True: an edge is a repeat iff its (source, target) pair came before -- the Javadoc's "a
+        neighborhood set for each vertex" and the reading TestDistinct pins.  per_vertex=False: iff its target
+        came before, whatever its source -- the literal DistinctEdgeMapper, which keeps ONE set of targets per
+        operator instance, at parallelism 1.
+
+        env.getParallelism() does not change the result.  Per vertex it cannot: keyBy(0) sends all edges of a
+        source to one subtask.  The literal mapper at parallelism P depends on which sources share a subtask,
+        i.e. on Flink's key -> subtask hash, which is not part of this package: a caller who wants that holds
+        P states (Engine.distinct("instance")) and routes by source."""
+        e = self.edges
+        n = len(e)
+        mb = self.context.getMicroBatch() or max(n, 1)
+        src, dst, val, idx = [], [], [], []
+        with self.context.engine.distinct("keyed" if per_vertex else "instance") as state:
+            for a in range(0, n, mb):
+                s, d, v, i = state.edges(e.src[a:a + mb], e.dst[a:a + mb], None if e.val is None else e.val[a:a + mb])
+                src.append(s); dst.append(d); val.append(v); idx.append(_to_np(i).astype(np.int64) + a)
+        if _is_torch(e.src):
+            import torch
+
+            cat = torch.cat
+        else:
+            cat = np.concatenate
+        if not src:
+            return SimpleEdgeStream(EdgeColumns(e.src[:0], e.dst[:0], None if e.val is None else e.val[:0],
+                                                None if e.ts is None else e.ts[:0]), self.context)
+        ts = None if e.ts is None else np.asarray(e.ts)[np.concatenate(idx)]
+        return SimpleEdgeStream(EdgeColumns(cat(src), cat(dst), None if e.val is None else cat(val), ts), self.context)
 
     def slice(self, size: Time, direction: EdgeDirection = EdgeDirection.OUT) -> "GraphWindowStream":
         """:139-171 tumbling windows keyed by the neighbour-key vertex."""

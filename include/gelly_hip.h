@@ -534,6 +534,66 @@ GS_API gs_status gs_cont_export(gs_ctx* ctx, const gs_cont* state, gs_vertex_out
  * counts >= 1 (GS_EINVAL otherwise), any order; records = the sum of the counts. */
 GS_API gs_status gs_cont_import(gs_ctx* ctx, gs_cont* state, const gs_partial_batch* rows);
 
+/* ---- distinct(): a device-resident edge set ------------------------------------------------------ */
+/* SimpleEdgeStream.distinct() (SimpleEdgeStream.java:305-327) is edges.keyBy(0).flatMap(DistinctEdgeMapper).
+ * The reference's code, Javadoc and test disagree about it, so a gs_distinct offers both readings as modes
+ * of one state:
+ *   GS_DISTINCT_KEYED     an edge is emitted iff the ordered pair (src, dst) has not been seen before, in this
+ *                         batch or an earlier one: the Javadoc's "a neighborhood set for each vertex"
+ *                         (:300-303) and the only reading TestDistinct's golden (TestDistinct.java:59-75) pins.
+ *   GS_DISTINCT_INSTANCE  an edge is emitted iff dst has not been seen before, whatever its source: the
+ *                         literal mapper (:313-327), which keeps ONE HashSet of targets per operator instance,
+ *                         at parallelism 1.  The literal behaviour at parallelism P is P such states with the
+ *                         edges routed by source; Flink's key -> subtask hash is not part of this library, so
+ *                         that routing is the caller's (unpinned here).
+ * In both modes the emitted edge is the first arrival, unchanged; emitted edges keep their arrival order;
+ * self-loops are ordinary edges; (a, b) and (b, a) are different pairs; every int64 is a legal id, -1
+ * included; and the concatenated output of a stream depends only on the stream, never on where it was cut
+ * into batches.  The state is a hash set in HBM (equality is always decided on the full ids, never on a
+ * hash) plus a log of the distinct edges in first-arrival order, grown by doubling.
+ * One state is used from one thread at a time, with a ctx of its device.  A call that returns GS_EINVAL,
+ * GS_ECAPACITY or GS_ENOMEM leaves the state exactly as it was: every allocation and argument check comes
+ * before the first write to the table.  A batch holds at most 2^32 - 1 edges (GS_EINVAL above: split it).
+ * Outputs are complete on return (host memory) or in the order of the ctx's stream (device memory). */
+typedef enum gs_distinct_mode { GS_DISTINCT_KEYED = 0, GS_DISTINCT_INSTANCE = 1 } gs_distinct_mode;
+typedef struct gs_distinct gs_distinct;
+/* Edge output: the k-th emitted edge in row k.  Each of the four columns may be NULL, and a NULL column is
+ * not written.  index[k] is the position inside this batch of the k-th emitted edge, for a caller that
+ * gathers further columns (timestamps).  val carries the batch's dtype and is copied bit for bit (a NaN
+ * keeps its payload). */
+typedef struct gs_edge_out {
+  int64_t* src;            /* [capacity] or NULL                                           */
+  int64_t* dst;            /* [capacity] or NULL                                           */
+  void* val;               /* [capacity] values of the batch's dtype, or NULL              */
+  uint64_t* index;         /* [capacity] arrival positions inside the batch, or NULL       */
+  uint64_t capacity;
+  uint64_t* n_out;         /* host pointer: edges written / needed                         */
+  int32_t mem;             /* gs_mem of the four columns                                   */
+  int32_t reserved;
+} gs_edge_out;
+/* An empty state of the given gs_distinct_mode.  A batch of n edges needs room for distinct + n edges
+ * before it runs (n bounds its new edges), so reserve_edges = the distinct edges expected plus one batch
+ * never grows (0 = smallest). */
+GS_API gs_status gs_distinct_create(gs_ctx* ctx, int32_t mode, uint64_t reserve_edges, gs_distinct** out);
+GS_API void gs_distinct_destroy(gs_distinct* state);
+/* One batch of the stream: out holds its edges never seen before, in arrival order.  Needs capacity >= n
+ * whenever a column is asked for: GS_ECAPACITY with *n_out = n otherwise (an upper bound, as
+ * gs_cont_vertices).  With all four columns NULL the call only updates the state and reports the count.
+ * out->val with a batch that has no values (GS_NONE or a NULL val) is GS_EINVAL. */
+GS_API gs_status gs_distinct_edges(gs_ctx* ctx, gs_distinct* state, const gs_edge_batch* batch, gs_edge_out* out);
+/* Distinct edges kept and records seen so far, duplicates included (either pointer may be NULL). */
+GS_API gs_status gs_distinct_size(const gs_distinct* state, uint64_t* distinct_edges, uint64_t* records);
+/* The table's slots and how often it has doubled (either pointer may be NULL); load = distinct / slots <= 1/2. */
+GS_API gs_status gs_distinct_capacity(const gs_distinct* state, uint64_t* slots, uint64_t* growths);
+/* Checkpoint: the distinct edges so far IN THE ORDER OF FIRST ARRIVAL, i.e. the operator's output stream
+ * so far.  Writes src and dst only (val or index non-NULL: GS_EINVAL).  capacity < the distinct edges:
+ * GS_ECAPACITY with *n_out = that number. */
+GS_API gs_status gs_distinct_export(gs_ctx* ctx, const gs_distinct* state, gs_edge_out* out);
+/* Restore a checkpoint into an EMPTY state (GS_EINVAL otherwise): rows->src / rows->dst in any order, a
+ * repeated row is taken once (rows->val is ignored); records = the distinct count.  The restored log keeps
+ * the rows' order. */
+GS_API gs_status gs_distinct_import(gs_ctx* ctx, gs_distinct* state, const gs_edge_batch* rows);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;

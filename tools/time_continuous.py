@@ -1,9 +1,10 @@
-"""Time of the continuous operators per micro-batch (not a bench line): gs_cont_degrees and gs_cont_vertices
+"""Time of the continuous operators per micro-batch (not a bench line): gs_cont_degrees, gs_cont_vertices and
+gs_distinct_edges (KEYED; src, dst and index columns out)
 on an R-MAT scale-22 stream cut into 8 batches of 2^22 edges (device columns, preallocated outputs,
 GS_DIR_ALL), against gs_window_csr with ALL on the same batches in the same process -- the same sort_window
-followed by a gather.  Device events around each call, after a warm-up pass over every batch; the three calls
-alternate batch by batch.  Two timed passes: states that start empty (the table grows while the stream
-runs) and states created with room for the stream's vertices (no growth).  Prints one JSON line.
+followed by a gather.  Device events around each call, after a warm-up pass over every batch; the four calls
+alternate batch by batch.  Two timed passes: states that start empty (the tables grow while the stream
+runs) and states created with room for the stream's vertices / edges (no growth).  Prints one JSON line.
 
     python tools/time_continuous.py [--scale 22] [--batches 8] [--log2-batch 22] [--passes 3]"""
 import argparse
@@ -42,6 +43,9 @@ def main():
     vo = L.GsVertexOut(ok.data_ptr(), ov.data_ptr(), R, ctypes.pointer(n_out), L.GS_MEM_DEVICE, 0)
     cso = L.GsCsrOut(ck.data_ptr(), co.data_ptr(), cn.data_ptr(), None, R, R, ctypes.pointer(nv), ctypes.pointer(nr),
                      L.GS_MEM_DEVICE, 0)
+    es, ed, ei = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    ne = ctypes.c_uint64(0)
+    eo = L.GsEdgeOut(es.data_ptr(), ed.data_ptr(), None, ei.data_ptr(), n, ctypes.pointer(ne), L.GS_MEM_DEVICE, 0)
     batches = [L.GsEdgeBatch(s.data_ptr(), d.data_ptr(), None, n, L.GS_NONE, L.GS_MEM_DEVICE, 0) for s, d in cols]
 
     def timed(f):
@@ -54,39 +58,50 @@ def main():
             raise pkg.GsError(st, lib.gs_last_error(eng.ctx).decode())
         return e0.elapsed_time(e1)
 
-    runs_per_batch = []
+    runs_per_batch, kept_per_batch = [], []
 
-    def one_pass(reserve):
-        """every batch through csr, a degree state and a vertex state; per-batch ms of each, the states' sizes"""
-        sd, sv = eng.continuous(reserve), eng.continuous(reserve)
-        ms = {"csr": [], "degrees": [], "vertices": []}
+    def one_pass(reserve, reserve_edges=0):
+        """every batch through csr, a degree state, a vertex state and an edge set; per-batch ms of each, the
+        states' sizes"""
+        sd, sv, se = eng.continuous(reserve), eng.continuous(reserve), eng.distinct("keyed", reserve_edges)
+        ms = {"csr": [], "degrees": [], "vertices": [], "distinct": []}
         runs_per_batch.clear()
+        kept_per_batch.clear()
         for b in batches:
             ms["csr"].append(timed(lambda: lib.gs_window_csr(eng.ctx, ctypes.byref(b), ALL, ctypes.byref(cso))))
             runs_per_batch.append(nv.value)   # the batch's distinct vertices: the lanes of the table kernel
             ms["degrees"].append(timed(lambda: lib.gs_cont_degrees(eng.ctx, sd.handle, ctypes.byref(b), ALL, ctypes.byref(vo))))
             ms["vertices"].append(timed(lambda: lib.gs_cont_vertices(eng.ctx, sv.handle, ctypes.byref(b), ctypes.byref(vo))))
+            ms["distinct"].append(timed(lambda: lib.gs_distinct_edges(eng.ctx, se.handle, ctypes.byref(b), ctypes.byref(eo))))
+            kept_per_batch.append(ne.value)
+        einfo = {"distinct": se.size()[0], "records": se.size()[1], "slots": se.capacity()[0], "growths": se.capacity()[1]}
+        se.close()
         info = {"distinct": sd.size()[0], "records": sd.size()[1], "slots": sd.capacity()[0], "growths": sd.capacity()[1]}
         sd.close()
         sv.close()
-        return ms, info
+        return ms, info, einfo
 
-    _, info = one_pass(0)   # warm-up: every shape once (code objects, workspace), and the stream's vertex count
+    _, info, _ = one_pass(0)   # warm-up: every shape once (code objects, workspace), and the stream's vertex count
     out = {"scale": a.scale, "batches": a.batches, "edges_per_batch": n, "records_per_batch": R, "passes": a.passes,
-           "distinct_per_batch": list(runs_per_batch)}
-    for name, reserve in (("growing", 0), ("reserved", 2 * info["distinct"])):
-        runs = [one_pass(reserve) for _ in range(a.passes)]
+           "distinct_per_batch": list(runs_per_batch), "kept_edges_per_batch": list(kept_per_batch)}
+    # an edge set that never grows: room for every edge of the stream plus one batch (gs_distinct_create)
+    for name, reserve, reserve_edges in (("growing", 0, 0), ("reserved", 2 * info["distinct"], (a.batches + 1) * n)):
+        runs = [one_pass(reserve, reserve_edges) for _ in range(a.passes)]
         res = {}
-        for k in ("csr", "degrees", "vertices"):
+        for k in ("csr", "degrees", "vertices", "distinct"):
             per_batch = [statistics.median(r[0][k][i] for r in runs) for i in range(a.batches)]
             total = [sum(r[0][k]) for r in runs]
             res[k] = {"ms_per_batch": [round(x, 3) for x in per_batch], "ms_stream_min_med_max":
                       [round(min(total), 3), round(statistics.median(total), 3), round(max(total), 3)],
                       "records_per_s": round(a.batches * R / (statistics.median(total) * 1e-3))}
-        for k in ("degrees", "vertices"):
+        res["distinct"]["edges_per_s"] = round(a.batches * n / (res["distinct"]["ms_stream_min_med_max"][1] * 1e-3))
+        del res["distinct"]["records_per_s"]   # its records are edges (no direction expansion)
+        for k in ("degrees", "vertices", "distinct"):
             res[k]["ratio_to_csr"] = round(res[k]["ms_stream_min_med_max"][1] / res["csr"]["ms_stream_min_med_max"][1], 3)
         st = runs[-1][1]
         res["table"] = dict(st, load_factor=round(st["distinct"] / st["slots"], 4))
+        et = runs[-1][2]
+        res["edge_table"] = dict(et, load_factor=round(et["distinct"] / et["slots"], 4))
         out[name] = res
     print(json.dumps(out))
     eng.close()
