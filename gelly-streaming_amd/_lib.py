@@ -26,6 +26,9 @@ GS_READBACK_STREAM, GS_READBACK_EARLY, GS_READBACK_EARLY_TIMEOUT = 0, 1, 2   # g
 GS_I32, GS_I64, GS_F32, GS_F64, GS_NONE = 0, 1, 2, 3, 4
 GS_OP_SUM, GS_OP_MIN, GS_OP_MAX, GS_OP_COUNT = 0, 1, 2, 3
 GS_DISTINCT_KEYED, GS_DISTINCT_INSTANCE = 0, 1   # gs_distinct_mode
+GS_TRISAMPLE_BROADCAST, GS_TRISAMPLE_INCIDENCE = 0, 1   # gs_trisample_mode
+GS_TRISAMPLE_TILE = 2048        # edges per tile of the streaming pass
+GS_TRISAMPLE_ROW_WORDS = 8      # int64 words of a sampler's checkpoint row
 STATUS_NAMES = {0: "GS_OK", -1: "GS_EINVAL", -2: "GS_ECAPACITY", -3: "GS_EDEVICE", -4: "GS_ECOMM",
                 -5: "GS_ENOMEM", -6: "GS_EUNSUPPORTED", -7: "GS_EAGAIN"}
 
@@ -52,7 +55,9 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_candidates_vertex_range", "gs_cont_create", "gs_cont_destroy", "gs_cont_size", "gs_cont_capacity",
            "gs_cont_degrees", "gs_cont_vertices", "gs_cont_export", "gs_cont_import",
            "gs_distinct_create", "gs_distinct_destroy", "gs_distinct_edges", "gs_distinct_size", "gs_distinct_capacity",
-           "gs_distinct_export", "gs_distinct_import")
+           "gs_distinct_export", "gs_distinct_import",
+           "gs_trisample_create", "gs_trisample_destroy", "gs_trisample_edges", "gs_trisample_size",
+           "gs_trisample_export", "gs_trisample_import")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -85,6 +90,11 @@ class GsVertexOut(ctypes.Structure):
 class GsEdgeOut(ctypes.Structure):   # gs_edge_out: the edges gs_distinct_edges / _export emit
     _fields_ = [("src", P), ("dst", P), ("val", P), ("index", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)),
                 ("mem", i32), ("reserved", i32)]
+
+
+class GsTrisampleHeader(ctypes.Structure):   # gs_trisample_header: a sampler checkpoint's parameters and counters
+    _fields_ = [("edges_seen", u64), ("beta_sum", i64), ("last_emitted", i64), ("samples", u64), ("first_sampler", u64),
+                ("vertex_count", u64), ("seed", u64), ("mode", i32), ("reserved", i32)]
 
 
 class GsDegreeOut(ctypes.Structure):
@@ -274,6 +284,12 @@ def load() -> ctypes.CDLL:
         "gs_distinct_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "gs_distinct_export": (st, [P, P, ctypes.POINTER(GsEdgeOut)]),
         "gs_distinct_import": (st, [P, P, ctypes.POINTER(GsEdgeBatch)]),
+        "gs_trisample_create": (st, [P, i32, u64, u64, u64, u64, ctypes.POINTER(P)]),
+        "gs_trisample_destroy": (None, [P]),
+        "gs_trisample_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsVertexOut)]),
+        "gs_trisample_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(i64)]),
+        "gs_trisample_export": (st, [P, P, ctypes.POINTER(GsTrisampleHeader), P, u64, i32, ctypes.POINTER(u64)]),
+        "gs_trisample_import": (st, [P, P, ctypes.POINTER(GsTrisampleHeader), P, u64, i32]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)

@@ -471,6 +471,8 @@ void gs_destroy(gs_ctx* c) {
     if (b.p) hipFree(b.p);
   for (DevBuf& b : c->ct)
     if (b.p) hipFree(b.p);
+  for (DevBuf& b : c->ts)
+    if (b.p) hipFree(b.p);
   for (DevBuf& b : c->tri_bd)
     if (b.p) hipFree(b.p);
   for (DevBuf& b : c->tri_rl)

@@ -692,6 +692,14 @@ class Engine:
         DistinctEdgeMapper at parallelism 1).  reserve_edges: the distinct edges expected plus one batch."""
         return DistinctState(self, mode, reserve_edges)
 
+    def triangle_sampler(self, mode: str, samples: int, vertex_count: int, seed: int = 0,
+                         first_sampler: int = 0) -> "TriangleSamplerState":
+        """gs_trisample_create: the samplers of one TriangleSampler subtask of BroadcastTriangleCount
+        (mode "broadcast") or IncidenceSamplingTriangleCount ("incidence"), in HBM across batches.  A caller
+        who mirrors parallelism P holds P states with disjoint sampler ids (first_sampler) and one
+        triangle_estimate.TriangleSummer."""
+        return TriangleSamplerState(self, mode, samples, vertex_count, seed, first_sampler)
+
     # -- multi-GPU keyBy halves (gs_dist.hip) --------------------------------------------------------
     def reduce_partials(self, src, dst, val, direction, op, nparts: int):
         """gs_window_reduce_partials: this slice's per-vertex partials grouped by owner (gs_owner_of).
@@ -1065,3 +1073,100 @@ class DistinctState:
         row taken once)."""
         b, keep, dev = self.engine._batch(src, dst, None)
         self.engine._check(self._L.gs_distinct_import(self.engine.ctx, self.handle, ctypes.byref(b)))
+
+
+class TriangleSamplerState:
+    """gs_trisample: `samples` samplers of the streaming triangle estimators (include/gelly_hip.h, "streaming
+    triangle-count estimators"), their state in HBM across calls.  Feed it the stream in batches of any size:
+    the concatenated records and the exported state depend only on the stream.  Columns are numpy arrays
+    (results come back as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
+
+    MODES = {"broadcast": L.GS_TRISAMPLE_BROADCAST, "incidence": L.GS_TRISAMPLE_INCIDENCE}
+    TILE = L.GS_TRISAMPLE_TILE
+
+    def __init__(self, engine: Engine, mode: str, samples: int, vertex_count: int, seed: int = 0, first_sampler: int = 0):
+        if mode not in self.MODES:
+            raise ValueError(f"mode: one of {sorted(self.MODES)}")
+        if samples < 0 or vertex_count < 0 or first_sampler < 0:
+            raise ValueError("samples, vertex_count and first_sampler are not negative")
+        self.engine = engine
+        self.mode = mode
+        self.samples = int(samples)
+        self._L = engine._L
+        h = ctypes.c_void_p()
+        engine._check(self._L.gs_trisample_create(engine.ctx, self.MODES[mode], int(samples), int(first_sampler),
+                                                  int(vertex_count), int(seed) & (2**64 - 1), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.gs_trisample_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def edges(self, src, dst, capacity: int = None):
+        """gs_trisample_edges: the TriangleEstimate records of the batch as (edge counts, local beta sums), in
+        emission order.  capacity: room for that many records (default: one per edge); a batch that emits
+        more is run again with the number it reported -- a call that fails leaves the state as it was."""
+        e = self.engine
+        b, keep, dev = e._batch(src, dst, None)
+        cap = max(int(b.n if capacity is None else capacity), 1)
+        for _ in range(2):
+            keys, vals = e._empty(dev, cap, np.int64), e._empty(dev, cap, np.int64)
+            n_out = ctypes.c_uint64(0)
+            vo = L.GsVertexOut(_ptr(keys), _ptr(vals), cap, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+            st = self._L.gs_trisample_edges(e.ctx, self.handle, ctypes.byref(b), ctypes.byref(vo))
+            if st != L.GS_ECAPACITY or capacity is not None:
+                break
+            cap = n_out.value
+        e._check(st)
+        return keys[:n_out.value], vals[:n_out.value]
+
+    def advance(self, src, dst) -> int:
+        """gs_trisample_edges without output columns: the batch only updates the state; returns the number
+        of records it would have emitted."""
+        e = self.engine
+        b, keep, dev = e._batch(src, dst, None)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(None, None, 0, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_trisample_edges(e.ctx, self.handle, ctypes.byref(b), ctypes.byref(vo)))
+        return n_out.value
+
+    def size(self):
+        """gs_trisample_size: (edges seen, local beta sum now)."""
+        n, s = ctypes.c_uint64(0), ctypes.c_int64(0)
+        self.engine._check(self._L.gs_trisample_size(self.handle, ctypes.byref(n), ctypes.byref(s)))
+        return n.value, s.value
+
+    def export(self, device: bool = False):
+        """gs_trisample_export: the checkpoint -- (header dict, rows [samples, 8] int64; numpy or, with
+        device=True, a CUDA tensor).  Row layout: include/gelly_hip.h, GS_TRISAMPLE_ROW_WORDS."""
+        e = self.engine
+        W = L.GS_TRISAMPLE_ROW_WORDS
+        rows = e._empty(device, self.samples * W, np.int64)
+        hdr = L.GsTrisampleHeader()
+        n_out = ctypes.c_uint64(0)
+        e._check(self._L.gs_trisample_export(e.ctx, self.handle, ctypes.byref(hdr), _ptr(rows), self.samples,
+                                             L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, ctypes.byref(n_out)))
+        header = {name: getattr(hdr, name) for name, _ in L.GsTrisampleHeader._fields_ if name != "reserved"}
+        return header, rows[:self.samples * W].reshape(self.samples, W)
+
+    def load(self, header: dict, rows):
+        """gs_trisample_import: restore a checkpoint into this, still fresh, state of the same parameters."""
+        dev = _is_torch(rows)
+        rows = rows.contiguous() if dev else np.ascontiguousarray(rows, dtype=np.int64)
+        hdr = L.GsTrisampleHeader(**{k: int(v) for k, v in header.items()})
+        n = int(rows.shape[0]) if len(rows.shape) == 2 else len(rows) // L.GS_TRISAMPLE_ROW_WORDS
+        self.engine._check(self._L.gs_trisample_import(self.engine.ctx, self.handle, ctypes.byref(hdr), _ptr(rows), n,
+                                                       L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST))

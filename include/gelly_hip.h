@@ -594,6 +594,76 @@ GS_API gs_status gs_distinct_export(gs_ctx* ctx, const gs_distinct* state, gs_ed
  * the rows' order. */
 GS_API gs_status gs_distinct_import(gs_ctx* ctx, gs_distinct* state, const gs_edge_batch* rows);
 
+/* ---- streaming triangle-count estimators: sampler state in HBM ----------------------------------- */
+/* example/BroadcastTriangleCount.java and example/IncidenceSamplingTriangleCount.java run `samples`
+ * independent samplers of the Buriol et al. estimator over an unbounded edge stream.  A gs_trisample holds
+ * the samplers of one TriangleSampler subtask (BroadcastTriangleCount.java:62-135) across batches and emits
+ * that subtask's TriangleEstimate records (edge count, local beta sum); TriangleSummer (:138-174) stays on
+ * the host.  The stream is fed in batches of any size: the concatenated records and the exported state
+ * depend only on the stream, never on where it is cut.
+ *
+ * Random numbers are counter-based and the library's own (the reference draws from Math.random(), so its
+ * output is not reproducible): r(seed, sampler, j, a) = mix(mix(mix(seed, sampler), j), a) with
+ * mix(s, i) = splitmix64 of s + (i + 1) * 0x9E3779B97F4A7C15, `sampler` the global sampler id
+ * (first_sampler + index), j the index of the sampler's replacement (0 = its first) and a the draw within
+ * it.  The positions at which a sampler replaces its edge are K_0 = 1 and
+ *   K_{j+1} = floor(K_j * 2^32 / ((r(seed, sampler, j, 0) >> 32) + 1)) + 1          (integers only),
+ * "never" above 2^31 - 1: P(K_{j+1} > m) = K_j / m, the product of the reference's per-edge coins
+ * (1 - 1/k for k = K_j + 1 .. m).  The third vertex of replacement j is mulhi64(r(seed, sampler, j, a),
+ * vertex_count) for a = 1, 2, ... until it differs from both endpoints.
+ *
+ * GS_TRISAMPLE_BROADCAST: one record after every edge at which the local beta sum differs from the last
+ * emitted one.  GS_TRISAMPLE_INCIDENCE: a record only when a sampler finds its triangle, with the sum as it
+ * stands at that sampler's turn (the edge's replacements of lower-numbered samplers included, those of
+ * higher-numbered ones not), if it differs from the last emitted one; several records may carry one edge count.
+ *
+ * One state from one thread at a time.  A call that fails with GS_EINVAL, GS_ECAPACITY or GS_ENOMEM leaves
+ * the state exactly as it was.  Outputs are complete on return (host memory) or in the order of the ctx's
+ * stream (device memory). */
+typedef enum gs_trisample_mode { GS_TRISAMPLE_BROADCAST = 0, GS_TRISAMPLE_INCIDENCE = 1 } gs_trisample_mode;
+typedef struct gs_trisample gs_trisample;
+/* edges per tile of the streaming pass (one block reads a tile at a time) */
+#define GS_TRISAMPLE_TILE 2048
+/* The checkpoint row of one sampler: 8 int64 words --
+ *   [0] srcVertex  [1] trgVertex  [2] thirdVertex (-1 before the first edge)
+ *   [3] flags: bit 0 srcEdgeFound, bit 1 trgEdgeFound, bit 2 beta
+ *   [4] replacements done (the j of the next one)  [5] position of the held edge (0 = none)
+ *   [6] position of the next replacement (2^31 = never)  [7] 0 */
+#define GS_TRISAMPLE_ROW_WORDS 8
+/* The checkpoint's header: the state's parameters and counters. */
+typedef struct gs_trisample_header {
+  uint64_t edges_seen;     /* edges of the stream so far (the reference's edgeCount)               */
+  int64_t beta_sum;        /* samplers with beta = 1                                               */
+  int64_t last_emitted;    /* the local beta sum of the last record (previousResult)               */
+  uint64_t samples;
+  uint64_t first_sampler;
+  uint64_t vertex_count;
+  uint64_t seed;
+  int32_t mode;            /* gs_trisample_mode                                                    */
+  int32_t reserved;
+} gs_trisample_header;
+/* `samples` samplers (1 .. 2^31 - 1) with the global ids first_sampler .. first_sampler + samples - 1: a
+ * caller holds P states of disjoint samplers where the reference runs at parallelism P, and its summer
+ * divides by the total.  vertex_count (3 .. 2^63 - 1): third vertices are drawn from [0, vertex_count). */
+GS_API gs_status gs_trisample_create(gs_ctx* ctx, int32_t mode, uint64_t samples, uint64_t first_sampler,
+                                     uint64_t vertex_count, uint64_t seed, gs_trisample** out);
+GS_API void gs_trisample_destroy(gs_trisample* state);
+/* One batch of the stream (batch->val is ignored; endpoints are arbitrary int64).  out->keys = edge counts,
+ * out->vals (I64) = local beta sums, in emission order.  capacity < the records: GS_ECAPACITY with *n_out =
+ * their number and the state unchanged.  keys and vals both NULL: the call only updates the state and
+ * reports the number.  A batch that takes the stream past 2^31 - 1 edges: GS_EINVAL (edgeCount is an int). */
+GS_API gs_status gs_trisample_edges(gs_ctx* ctx, gs_trisample* state, const gs_edge_batch* batch, gs_vertex_out* out);
+/* Edges seen and the local beta sum now (either pointer may be NULL). */
+GS_API gs_status gs_trisample_size(const gs_trisample* state, uint64_t* edges_seen, int64_t* beta_sum);
+/* Checkpoint: the header and `samples` rows of GS_TRISAMPLE_ROW_WORDS int64 (gs_mem `mem`).  capacity_rows <
+ * samples: GS_ECAPACITY with *n_out = samples. */
+GS_API gs_status gs_trisample_export(gs_ctx* ctx, const gs_trisample* state, gs_trisample_header* header, int64_t* rows,
+                                     uint64_t capacity_rows, int32_t mem, uint64_t* n_out);
+/* Restore a checkpoint into a FRESH state (no edge seen) of the same mode, samples, first_sampler,
+ * vertex_count and seed: GS_EINVAL otherwise, and for rows that no run can have written. */
+GS_API gs_status gs_trisample_import(gs_ctx* ctx, gs_trisample* state, const gs_trisample_header* header,
+                                     const int64_t* rows, uint64_t n_rows, int32_t mem);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;

@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--log2-batch", type=int, default=22)
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--legs", default="tables,trisample")
+    ap.add_argument("--samples", default="10000,1000000")
     a = ap.parse_args()
     pkg = ge.load_package()
     L = pkg._lib
@@ -81,9 +83,41 @@ def main():
         sv.close()
         return ms, info, einfo
 
+    def trisample_pass(samples):
+        """every batch through csr and a fresh sampler state; per-batch ms of each, records per batch, the state's size"""
+        st = eng.triangle_sampler("broadcast", samples, 1 << a.scale, 0x5A3)
+        ms, recs = {"csr": [], "trisample": []}, []
+        for b in batches:
+            ms["csr"].append(timed(lambda: lib.gs_window_csr(eng.ctx, ctypes.byref(b), ALL, ctypes.byref(cso))))
+            ms["trisample"].append(timed(lambda: lib.gs_trisample_edges(eng.ctx, st.handle, ctypes.byref(b), ctypes.byref(vo))))
+            recs.append(n_out.value)
+        size = st.size()
+        st.close()
+        return ms, recs, size
+
+    legs = a.legs.split(",")
+    out = {"scale": a.scale, "batches": a.batches, "edges_per_batch": n, "records_per_batch": R, "passes": a.passes}
+    if "trisample" in legs:
+        out["trisample"] = {}
+        for samples in (int(x) for x in a.samples.split(",")):
+            trisample_pass(samples)   # warm-up
+            runs = [trisample_pass(samples) for _ in range(a.passes)]
+            res = {"records_per_batch": runs[-1][1], "edges_seen": runs[-1][2][0], "beta_sum": runs[-1][2][1]}
+            for k in ("csr", "trisample"):
+                per_batch = [statistics.median(r[0][k][i] for r in runs) for i in range(a.batches)]
+                res[k] = {"ms_per_batch": [round(x, 3) for x in per_batch],
+                          "ms_later_batches_median": round(statistics.median(per_batch[1:] or per_batch), 3)}
+            res["ratio_to_csr_first_batch"] = round(res["trisample"]["ms_per_batch"][0] / res["csr"]["ms_per_batch"][0], 3)
+            res["ratio_to_csr_later_batches"] = round(res["trisample"]["ms_later_batches_median"] /
+                                                      res["csr"]["ms_later_batches_median"], 3)
+            res["edges_per_s_later_batches"] = round(n / (res["trisample"]["ms_later_batches_median"] * 1e-3))
+            out["trisample"][str(samples)] = res
+    if "tables" not in legs:
+        print(json.dumps(out))
+        eng.close()
+        return
     _, info, _ = one_pass(0)   # warm-up: every shape once (code objects, workspace), and the stream's vertex count
-    out = {"scale": a.scale, "batches": a.batches, "edges_per_batch": n, "records_per_batch": R, "passes": a.passes,
-           "distinct_per_batch": list(runs_per_batch), "kept_edges_per_batch": list(kept_per_batch)}
+    out.update({"distinct_per_batch": list(runs_per_batch), "kept_edges_per_batch": list(kept_per_batch)})
     # an edge set that never grows: room for every edge of the stream plus one batch (gs_distinct_create)
     for name, reserve, reserve_edges in (("growing", 0, 0), ("reserved", 2 * info["distinct"], (a.batches + 1) * n)):
         runs = [one_pass(reserve, reserve_edges) for _ in range(a.passes)]
