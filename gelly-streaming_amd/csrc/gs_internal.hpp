@@ -102,7 +102,7 @@ struct gs_ctx {
   // triangles
   gs::DevBuf tri_loops, tri_tiles, tri_sfx, tri_nbr, tri_heavy, tri_range, tri_queue, tri_hwork;
   gs::DevBuf tri_d[10];          // split-window triangles (gs_window_triangles_dist)
-  gs::DevBuf cc[4];              // connected components (gs_components.hip; [3]: the giant tree's bits)
+  gs::DevBuf cc[4];              // union-find aggregations (gs_cc_common.hpp; [3]: the signed state's signs)
   gs::DevBuf ct[5];              // continuous streams (gs_continuous.hip): run keys, offsets, bases, flags, scan;
                                  // gs_distinct.hip: [0] held slots, [3] keep flags, [4] their scan
   gs::DevBuf ts[12];             // sampling triangle estimators (gs_trisample.hip): epochs, wanted table, events

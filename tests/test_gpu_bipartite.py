@@ -161,6 +161,58 @@ def test_accumulation_over_windows(engine, oracle):
     _failed(engine.bipartite(s[:100], d[:100], bad))
 
 
+# ---- the two-phase unions with a previous state as the larger segment, the one whose sources feed the giant
+# tree's sample: R-MAT s18 made bipartite, cut into 200 000 + 8 000 edges.  Window 1 touches 93 263 vertices, so
+# window 2 is 101 263 constraints (>= 65 536, the two-phase threshold), most of them state rows
+@functools.lru_cache(maxsize=None)
+def _state_windows(sparse):
+    import __graft_entry__ as ge
+    s, d = ge.load_oracle().gen_rmat(18, 208_000, 0x5EED0F)
+    s, d = s * 2, d * 2 + 1
+    if sparse:
+        s, d = s * 7_919_000_003 - (1 << 61), d * 7_919_000_003 - (1 << 61)
+    w1, w2 = (s[:200_000], d[:200_000]), (s[200_000:], d[200_000:])
+    want1 = canonical(*w1)
+    want2 = canonical(*w2, want1)
+    assert want1[0] and want2[0] and len(want1[1]) == 93_263
+    assert all(np.array_equal(x, y) for x, y in zip(want2[1:], canonical(s, d)[1:]))   # = the state of all the edges
+    for a in w1 + w2 + want1[1:] + want2[1:]:
+        a.setflags(write=False)
+    return w1, w2, want1, want2
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["direct", "relabel"])
+def test_two_phase_with_state(engine, sparse):
+    w1, w2, want1, want2 = _state_windows(sparse)
+    got1 = engine.bipartite(*_dev(*w1))
+    _same(got1, want1)
+    got2 = engine.bipartite(*_dev(*w2), got1)   # the state as device tensors
+    _same(got2, want2)
+    t = engine.stage_times()
+    assert t.path == 5 and t.records == len(w2[0]) + len(want1[1]) and t.vertices == len(want2[1])
+    _same(engine.bipartite(*w2, tuple(_np(x) for x in got1)), want2)   # as host arrays
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["direct", "relabel"])
+def test_two_phase_with_state_one_bad_edge(engine, sparse):
+    """Window 2 with one more edge, between two vertices that window 1's state puts on the same side of its
+    largest component and that no edge of window 2 touches: only the state rows' signs can decide it."""
+    (s1, d1), (s2, d2), want1, _ = _state_windows(sparse)
+    _, v, lab, sign = want1
+    labels, counts = np.unique(lab, return_counts=True)
+    side = v[(lab == labels[np.argmax(counts)]) & (sign == 1) & ~np.isin(v, np.concatenate([s2, d2]))]
+    rng = np.random.default_rng(0x5EED0F + sparse)
+    a, b = rng.choice(side, 2, replace=False)
+    at = int(rng.integers(0, len(s2) + 1))
+    s2, d2 = np.insert(s2, at, a), np.insert(d2, at, b)
+    assert not canonical(s2, d2, want1)[0]
+    bad = engine.bipartite(*_dev(s2, d2), (True,) + _dev(*want1[1:]))
+    _failed(bad)
+    _failed(engine.bipartite(s2, d2, want1))                  # host columns and state
+    _failed(engine.bipartite(*_dev(s1[:100], d1[:100]), bad))   # the next window stays failed
+    _failed(engine.bipartite(s1[:100], d1[:100], bad))
+
+
 def test_capacity_error_reports_the_rows_needed(pkg, engine):
     from gelly_streaming_amd import _lib as L
     s, d, want = _graph("s12", False)

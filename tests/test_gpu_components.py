@@ -67,6 +67,28 @@ def test_components_accumulate_over_windows(engine, oracle):
     _same(state_g, oracle.components(s, d))                    # = the components of all the edges
 
 
+@pytest.mark.parametrize("sparse", [False, True], ids=["direct", "relabel"])
+def test_components_two_phase_with_state(engine, oracle, sparse):
+    """The two-phase unions with a previous state as the larger segment, the one whose sources feed the giant
+    tree's sample: R-MAT s18 cut into 200 000 + 8 000 edges.  Window 1 leaves 65 236 state rows, so window 2
+    is 73 236 records (>= 65 536, the two-phase threshold) with more state rows than edges, and it merges
+    components of the state (999 before, 974 after)."""
+    s, d = oracle.gen_rmat(18, 208_000, 0x5EED0F)
+    if sparse:                                                  # negative and 64-bit spread ids: the relabel path
+        s, d = s * 7_919_000_003 - (1 << 61), d * 7_919_000_003 - (1 << 61)
+    (s1, d1), (s2, d2) = (s[:200_000], d[:200_000]), (s[200_000:], d[200_000:])
+    want1 = oracle.components(s1, d1)
+    want2 = oracle.components(s2, d2, want1)
+    assert len(want1[0]) == 65_236 > len(s2) and len(want1[0]) + len(s2) >= 65_536
+    assert (len(np.unique(want1[1])), len(np.unique(want2[1]))) == (999, 974)
+    got1 = engine.components(torch.from_numpy(s1).cuda(), torch.from_numpy(d1).cuda())
+    _same(got1, want1)
+    got2 = engine.components(torch.from_numpy(s2).cuda(), torch.from_numpy(d2).cuda(), got1)   # the state as device tensors
+    _same(got2, want2)
+    _same(engine.components(s2, d2, tuple(x.cpu().numpy() for x in got1)), want2)              # as host arrays
+    _same(got2, oracle.components(s, d))                        # = the components of all the edges
+
+
 def test_components_config_size(engine, oracle):
     """A large window (R-MAT s20, 2^24 edges): the partition equals the oracle's."""
     s, d = oracle.gen_rmat(20, 1 << 24, 0x5EED0C)

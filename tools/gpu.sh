@@ -13,7 +13,8 @@
 #   ktrace  TAG NAME [args]     the kernel trace of any bench line
 #   envab   TAG "base K=V .." [args] A/B of environment knobs, alternated twice on one box
 #   ab      TAG "V1 V2.." [args] A/B of tuning builds (csrc/Makefile bvariant / variant -> variants/NAME; "base" =
-#                               the in-tree library): bench lines alternated twice on one box -> ab_NAME_REP.json
+#                               the in-tree library): bench lines alternated twice (AB_REPS times) on one box
+#                               -> ab_NAME_REP.json
 #
 # Every GPU step has its own time limit and the chain stops at the first failure (set -e): after a
 # fault, an abort or a timeout nothing more runs on the GPU in that call.
@@ -56,7 +57,7 @@ case $MODE in
     pmc pmc_tri_s$S/sq "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES" $A --windows 1 ;;
   ab)
     VARIANTS=$1; shift
-    for rep in 1 2; do
+    for rep in $(seq "${AB_REPS:-2}"); do
       for v in $VARIANTS; do
         if [ "$v" = base ]; then lib=gelly-streaming_amd/libgellyhip.so; else lib=gelly-streaming_amd/variants/$v/libgellyhip.so; fi
         GELLY_HIP_LIB=$lib bench ab_${v}_$rep "$@" --no-cpu-baseline
@@ -97,7 +98,7 @@ case $MODE in
     # A/B of library knobs read from the environment ("base" = none; e.g. "base GS_TRI_OKEYS_PART=0"),
     # alternated twice on one box -> ab_NAME_REP.json
     VARIANTS=$1; shift
-    for rep in 1 2; do
+    for rep in $(seq "${AB_REPS:-2}"); do
       for v in $VARIANTS; do
         if [ "$v" = base ]; then bench ab_base_$rep "$@" --no-cpu-baseline
         else ( export "$v"; bench "ab_${v//=/_}_$rep" "$@" --no-cpu-baseline ); fi
