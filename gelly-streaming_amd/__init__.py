@@ -11,7 +11,8 @@ The directory name contains a hyphen, so it is loaded by path:
 or with ``load_package()`` from __graft_entry__.py.
 """
 from ._lib import GsError, load as load_library  # noqa: F401
-from .engine import CommGroup, ContinuousState, DistinctState, Engine, StageTimes, TriangleSamplerState  # noqa: F401
+from .engine import (CommGroup, ContinuousState, DistinctState, Engine, StageTimes, TriangleSamplerState,  # noqa: F401
+                     WeightedMatchingState)
 from .functions import (Collector, CountFold, CountReduce, DegreeMaxNeighborFold, EdgesApply, EdgesFold,  # noqa: F401
                         EdgesReduce, MaxReduce, MaxValuesFold, MinReduce, MinValuesFold, SumReduce, SumValuesFold)
 from .stream import (AscendingTimestampExtractor, DataStream, EdgeColumns, EdgeDirection,  # noqa: F401
@@ -20,6 +21,7 @@ from .stream import (AscendingTimestampExtractor, DataStream, EdgeColumns, EdgeD
 from .triangles import CountTriangles, GenerateCandidateEdges, window_triangles  # noqa: F401
 from .triangle_estimate import (TriangleSummer, broadcast_triangle_count,  # noqa: F401
                                 incidence_sampling_triangle_count)
+from .matching import MatchingEvent, centralized_weighted_matching  # noqa: F401
 from .aggregation import BipartitenessCheck, Candidates, ConnectedComponents, WindowGraphAggregation  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

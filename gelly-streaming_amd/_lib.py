@@ -27,6 +27,7 @@ GS_I32, GS_I64, GS_F32, GS_F64, GS_NONE = 0, 1, 2, 3, 4
 GS_OP_SUM, GS_OP_MIN, GS_OP_MAX, GS_OP_COUNT = 0, 1, 2, 3
 GS_DISTINCT_KEYED, GS_DISTINCT_INSTANCE = 0, 1   # gs_distinct_mode
 GS_TRISAMPLE_BROADCAST, GS_TRISAMPLE_INCIDENCE = 0, 1   # gs_trisample_mode
+GS_MATCH_ADD, GS_MATCH_REMOVE = 0, 1   # gs_match_event: MatchingEvent.Type ordinals
 GS_TRISAMPLE_TILE = 2048        # edges per tile of the streaming pass
 GS_TRISAMPLE_ROW_WORDS = 8      # int64 words of a sampler's checkpoint row
 STATUS_NAMES = {0: "GS_OK", -1: "GS_EINVAL", -2: "GS_ECAPACITY", -3: "GS_EDEVICE", -4: "GS_ECOMM",
@@ -57,7 +58,9 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_distinct_create", "gs_distinct_destroy", "gs_distinct_edges", "gs_distinct_size", "gs_distinct_capacity",
            "gs_distinct_export", "gs_distinct_import",
            "gs_trisample_create", "gs_trisample_destroy", "gs_trisample_edges", "gs_trisample_size",
-           "gs_trisample_export", "gs_trisample_import")
+           "gs_trisample_export", "gs_trisample_import",
+           "gs_match_create", "gs_match_destroy", "gs_match_edges", "gs_match_size", "gs_match_capacity",
+           "gs_match_last_batch", "gs_match_export", "gs_match_import")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -90,6 +93,11 @@ class GsVertexOut(ctypes.Structure):
 class GsEdgeOut(ctypes.Structure):   # gs_edge_out: the edges gs_distinct_edges / _export emit
     _fields_ = [("src", P), ("dst", P), ("val", P), ("index", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)),
                 ("mem", i32), ("reserved", i32)]
+
+
+class GsMatchOut(ctypes.Structure):   # gs_match_out: the MatchingEvents gs_match_edges emits
+    _fields_ = [("type", P), ("src", P), ("dst", P), ("val", P), ("index", P), ("capacity", u64),
+                ("n_out", ctypes.POINTER(u64)), ("mem", i32), ("reserved", i32)]
 
 
 class GsTrisampleHeader(ctypes.Structure):   # gs_trisample_header: a sampler checkpoint's parameters and counters
@@ -290,6 +298,14 @@ def load() -> ctypes.CDLL:
         "gs_trisample_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(i64)]),
         "gs_trisample_export": (st, [P, P, ctypes.POINTER(GsTrisampleHeader), P, u64, i32, ctypes.POINTER(u64)]),
         "gs_trisample_import": (st, [P, P, ctypes.POINTER(GsTrisampleHeader), P, u64, i32]),
+        "gs_match_create": (st, [P, u64, ctypes.POINTER(P)]),
+        "gs_match_destroy": (None, [P]),
+        "gs_match_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsMatchOut)]),
+        "gs_match_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i64)]),
+        "gs_match_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_match_last_batch": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_match_export": (st, [P, P, ctypes.POINTER(GsEdgeOut)]),
+        "gs_match_import": (st, [P, P, ctypes.POINTER(GsEdgeBatch)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)

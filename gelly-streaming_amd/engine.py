@@ -103,7 +103,7 @@ def _out_dtypes():
         import torch
 
         _OUT_DTYPES = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32,
-                       np.float64: torch.float64}
+                       np.float64: torch.float64, np.uint8: torch.uint8}
     return _OUT_DTYPES
 
 
@@ -692,6 +692,12 @@ class Engine:
         DistinctEdgeMapper at parallelism 1).  reserve_edges: the distinct edges expected plus one batch."""
         return DistinctState(self, mode, reserve_edges)
 
+    def weighted_matching(self, reserve_vertices: int = 0) -> "WeightedMatchingState":
+        """gs_match_create: an empty device-resident matching for example/CentralizedWeightedMatching (one
+        WeightedMatchingFlatMapper, parallelism 1).  reserve_vertices: the vertices expected plus two per edge
+        of one batch."""
+        return WeightedMatchingState(self, reserve_vertices)
+
     def triangle_sampler(self, mode: str, samples: int, vertex_count: int, seed: int = 0,
                          first_sampler: int = 0) -> "TriangleSamplerState":
         """gs_trisample_create: the samplers of one TriangleSampler subtask of BroadcastTriangleCount
@@ -1073,6 +1079,121 @@ class DistinctState:
         row taken once)."""
         b, keep, dev = self.engine._batch(src, dst, None)
         self.engine._check(self._L.gs_distinct_import(self.engine.ctx, self.handle, ctypes.byref(b)))
+
+
+class WeightedMatchingState:
+    """gs_match: the matching of one CentralizedWeightedMatching mapper (include/gelly_hip.h,
+    "CentralizedWeightedMatching") -- per vertex its partner, the edge's value and which end it is, in HBM across
+    calls.  Feed it the stream in batches of any size: the concatenated events depend only on the stream.
+    Columns are numpy arrays (results come back as numpy) or CUDA tensors of the engine's device (results stay
+    in HBM); values are int64 (Edge<Long, Long>)."""
+
+    COLUMNS = ("type", "src", "dst", "val", "index")
+    _DTYPES = {"type": np.uint8, "src": np.int64, "dst": np.int64, "val": np.int64, "index": np.int64}
+
+    def __init__(self, engine: Engine, reserve_vertices: int = 0):
+        self.engine = engine
+        self._L = engine._L
+        h = ctypes.c_void_p()
+        engine._check(self._L.gs_match_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.gs_match_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def edges(self, src, dst, val, out=None, capacity: int = None, columns=COLUMNS):
+        """gs_match_edges: the MatchingEvents of the batch in stream order as (type, src, dst, val, index) --
+        type 0 = ADD, 1 = REMOVE (uint8), index the position inside the batch of the arriving edge that caused
+        the event.  columns: the columns asked for (the others come back as None; none at all: the batch only
+        updates the state).  out: optional (type, src, dst, val, index) device tensors, reused across batches
+        (None for a column not asked for).  capacity: room for that many events (default: two per edge -- over
+        a stream REMOVEs never outnumber ADDs -- and a batch that emits more, at most 3n over a full matching,
+        runs again with the number it reported: a call that fails leaves the state as it was); with out, the
+        shortest tensor's length."""
+        e = self.engine
+        b, keep, dev = e._batch(src, dst, val)
+        want = [k in columns for k in self.COLUMNS]
+        dts = [self._DTYPES[k] for k in self.COLUMNS]
+        if out is not None:
+            if len(out) != 5 or [t is not None for t in out] != want:
+                raise ValueError("out: (type, src, dst, val, index), None exactly for the columns not asked for")
+            given = [t for t in out if t is not None]
+            e._check_out(given, dev, tuple(d for d, w in zip(dts, want) if w))
+            cap = min([t.numel() for t in given], default=0)
+            if capacity is not None:
+                cap = min(cap, int(capacity))
+        else:
+            cap = int(2 * b.n if capacity is None else capacity)
+        retry = out is None and capacity is None
+        for _ in range(2):
+            cols = list(out) if out is not None else [e._empty(dev, cap, d) if w else None for d, w in zip(dts, want)]
+            n_out = ctypes.c_uint64(0)
+            mo = L.GsMatchOut(*[_ptr(t) for t in cols], cap, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+            st = self._L.gs_match_edges(e.ctx, self.handle, ctypes.byref(b), ctypes.byref(mo))
+            if st != L.GS_ECAPACITY or not retry:
+                break
+            cap = n_out.value
+        self.last_events = n_out.value
+        e._check(st)
+        k = n_out.value
+        return tuple(None if t is None else t[:k] for t in cols)
+
+    def advance(self, src, dst, val) -> int:
+        """gs_match_edges without output columns: the batch only updates the state; returns the number of
+        events it would have emitted."""
+        self.edges(src, dst, val, columns=())
+        return self.last_events
+
+    def size(self):
+        """gs_match_size: (edges of M, records seen, wrapped int64 sum of M's values)."""
+        m, r, w = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int64(0)
+        self.engine._check(self._L.gs_match_size(self.handle, ctypes.byref(m), ctypes.byref(r), ctypes.byref(w)))
+        return m.value, r.value, w.value
+
+    def capacity(self):
+        """gs_match_capacity: (slots of the vertex table, doublings so far)."""
+        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_match_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
+        return s.value, g.value
+
+    def last_batch(self):
+        """gs_match_last_batch: {rounds, block_iterations, pending_after: {1, 2, 4, 8: edges}} of the last batch."""
+        r, bi, pa = ctypes.c_uint64(0), ctypes.c_uint64(0), (ctypes.c_uint64 * 4)()
+        self.engine._check(self._L.gs_match_last_batch(self.handle, ctypes.byref(r), ctypes.byref(bi), pa))
+        return {"rounds": r.value, "block_iterations": bi.value, "pending_after": {1 << k: pa[k] for k in range(4)}}
+
+    def export(self, device: bool = False):
+        """gs_match_export: the checkpoint -- M as (src, dst, val), ascending by (src, dst); numpy or
+        (device=True) CUDA tensors."""
+        e = self.engine
+        M = self.size()[0]
+        src, dst, val = (e._empty(device, M, np.int64) for _ in range(3))
+        n_out = ctypes.c_uint64(0)
+        eo = L.GsEdgeOut(_ptr(src), _ptr(dst), _ptr(val), None, M, ctypes.pointer(n_out),
+                         L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_match_export(e.ctx, self.handle, ctypes.byref(eo)))
+        n = n_out.value
+        return src[:n], dst[:n], val[:n]
+
+    def import_(self, src, dst, val):
+        """gs_match_import: restore a checkpoint into this, still empty, state (rows in any order; rows that
+        share an endpoint are refused)."""
+        b, keep, dev = self.engine._batch(src, dst, val)
+        self.engine._check(self._L.gs_match_import(self.engine.ctx, self.handle, ctypes.byref(b)))
 
 
 class TriangleSamplerState:

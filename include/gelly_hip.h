@@ -664,6 +664,70 @@ GS_API gs_status gs_trisample_export(gs_ctx* ctx, const gs_trisample* state, gs_
 GS_API gs_status gs_trisample_import(gs_ctx* ctx, gs_trisample* state, const gs_trisample_header* header,
                                      const int64_t* rows, uint64_t n_rows, int32_t mem);
 
+/* ---- CentralizedWeightedMatching: a device-resident streaming matching ---------------------------- */
+/* example/CentralizedWeightedMatching.java:67-108 keeps a set M of edges (src, dst, val), val a Java Long, in
+ * one WeightedMatchingFlatMapper (parallelism 1) and emits MatchingEvents (MatchingEvent.java:24-42).  For each
+ * arriving edge e = (u, v, w): C = the edges of M that share an endpoint with e (direction ignored), sum = the
+ * sum of their values; if w > 2 * sum, REMOVE c is emitted for every c in C, C leaves M, e enters it and ADD e
+ * is emitted; otherwise nothing happens.  The arithmetic is Java long: sum and 2 * sum wrap, the comparison is
+ * signed, and no sign is assumed (a negative w passes w > 2w against an identical stored edge).  M is always
+ * a matching, so |C| <= 2; u matched to v, or a stored self-loop, is ONE colliding edge.  Self-loops and
+ * repeated edges are ordinary edges; every int64 is a legal id, -1 included.
+ *
+ * Event order.  Per arriving edge the events are the reference's AS A SET, and all REMOVEs of an edge precede
+ * its ADD, as in the reference.  When an edge removes two, the reference emits them in HashSet<Edge> iteration
+ * order, which depends on Flink's Tuple3.hashCode and on the set's whole insertion history and is not pinned
+ * by anything in the reference; this library fixes a canonical order instead: the edge matched at the
+ * arriving edge's src first, then the one at its dst.  A REMOVE carries the stored edge's own (src, dst, val),
+ * not the arriving edge's orientation.
+ *
+ * A gs_match holds the matching per vertex in HBM across calls; the stream is fed in batches of any size and
+ * the concatenated events depend only on the stream, never on where it was cut.  The operator is parallelism
+ * 1, as in the reference.  One state is used from one thread at a time, with a ctx of its device.  A call
+ * that fails with GS_EINVAL, GS_ECAPACITY, GS_EUNSUPPORTED or GS_ENOMEM leaves the state exactly as it was.
+ * A batch holds at most 2^32 - 1 edges.  Outputs are complete on return (host memory) or in the order of the
+ * ctx's stream (device memory). */
+typedef enum gs_match_event { GS_MATCH_ADD = 0, GS_MATCH_REMOVE = 1 } gs_match_event;   /* MatchingEvent.Type ordinals */
+typedef struct gs_match gs_match;
+/* Event output: the k-th event of the batch in row k, in stream order.  Each of the five columns may be NULL,
+ * and a NULL column is not written.  index[k] is the position inside this batch of the arriving edge that
+ * caused event k. */
+typedef struct gs_match_out {
+  uint8_t* type;           /* [capacity] gs_match_event, or NULL                           */
+  int64_t* src;            /* [capacity] or NULL                                           */
+  int64_t* dst;            /* [capacity] or NULL                                           */
+  int64_t* val;            /* [capacity] or NULL                                           */
+  uint64_t* index;         /* [capacity] or NULL                                           */
+  uint64_t capacity;
+  uint64_t* n_out;         /* host pointer: events written / needed                        */
+  int32_t mem;             /* gs_mem of the five columns                                   */
+  int32_t reserved;
+} gs_match_out;
+/* An empty matching with room for reserve_vertices vertices before its first growth (0 = smallest).  A batch
+ * of n edges needs room for the vertices seen so far + 2n before it runs. */
+GS_API gs_status gs_match_create(gs_ctx* ctx, uint64_t reserve_vertices, gs_match** out);
+GS_API void gs_match_destroy(gs_match* state);
+/* One batch of the stream.  batch->val_dtype must be GS_I64 with a non-NULL val: GS_EUNSUPPORTED otherwise.
+ * A capacity smaller than the batch's events (when a column is asked for): GS_ECAPACITY with *n_out = their
+ * number and the state unchanged; 3n always suffices.  With all five columns NULL the call only updates the
+ * state and reports the number. */
+GS_API gs_status gs_match_edges(gs_ctx* ctx, gs_match* state, const gs_edge_batch* batch, gs_match_out* out);
+/* Edges of M, records seen, and the wrapped int64 sum of M's values (each pointer may be NULL). */
+GS_API gs_status gs_match_size(const gs_match* state, uint64_t* matched_edges, uint64_t* records, int64_t* total_weight);
+/* The vertex table's slots and how often it has doubled (either pointer may be NULL). */
+GS_API gs_status gs_match_capacity(const gs_match* state, uint64_t* slots, uint64_t* growths);
+/* How the last gs_match_edges call went (each pointer may be NULL): its rounds, its blocking iterations, and
+ * the edges still pending after rounds 1, 2, 4 and 8 (pending_after[4]; 0 for a round it did not need). */
+GS_API gs_status gs_match_last_batch(const gs_match* state, uint64_t* rounds, uint64_t* block_iterations,
+                                     uint64_t* pending_after);
+/* Checkpoint: M as (src, dst, val) rows (val I64), ascending by (src, dst); index must be NULL (GS_EINVAL).
+ * capacity < |M|: GS_ECAPACITY with *n_out = |M|. */
+GS_API gs_status gs_match_export(gs_ctx* ctx, const gs_match* state, gs_edge_out* out);
+/* Restore a checkpoint into an EMPTY state (GS_EINVAL otherwise): I64 values, rows in any order.  Rows that
+ * share an endpoint are no matching: GS_EINVAL, the state unchanged.  A self-loop row is fine.  records = the
+ * number of rows. */
+GS_API gs_status gs_match_import(gs_ctx* ctx, gs_match* state, const gs_edge_batch* rows);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;

@@ -5,12 +5,17 @@ GS_DIR_ALL), against gs_window_csr with ALL on the same batches in the same proc
 followed by a gather.  Device events around each call, after a warm-up pass over every batch; the four calls
 alternate batch by batch.  Two timed passes: states that start empty (the tables grow while the stream
 runs) and states created with room for the stream's vertices / edges (no growth).  Prints one JSON line.
+The `matching` leg: gs_match_edges (all five event columns out, room for 3n events) on the same batches with
+16-bit values, a cold state and then a second pass of the same stream over the warm state -- per batch ms,
+edges/s, rounds, blocking iterations, edges pending after rounds 1, 2, 4 and 8, events, and the ratio to
+gs_window_csr -- next to one host thread running tools/matching_cpu.cpp on the same stream.
 
     python tools/time_continuous.py [--scale 22] [--batches 8] [--log2-batch 22] [--passes 3]"""
 import argparse
 import ctypes
 import json
 import statistics
+import subprocess
 import sys
 from pathlib import Path
 
@@ -28,7 +33,7 @@ def main():
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--log2-batch", type=int, default=22)
     ap.add_argument("--passes", type=int, default=3)
-    ap.add_argument("--legs", default="tables,trisample")
+    ap.add_argument("--legs", default="tables,trisample,matching")
     ap.add_argument("--samples", default="10000,1000000")
     a = ap.parse_args()
     pkg = ge.load_package()
@@ -95,8 +100,66 @@ def main():
         st.close()
         return ms, recs, size
 
+    def matching_leg():
+        """a cold state, then the same stream again over the warm state; one host thread on the same stream"""
+        import numpy as np
+
+        vals = [eng.generate_values(n, 0x5EEDC3, first_edge=k * n) & 0xFFFF for k in range(a.batches)]
+        mb = [L.GsEdgeBatch(s.data_ptr(), d.data_ptr(), v.data_ptr(), n, L.GS_I64, L.GS_MEM_DEVICE, 0)
+              for (s, d), v in zip(cols, vals)]
+        mt = torch.empty(3 * n, dtype=torch.uint8, device=dev)
+        ms_, md, mv, mi = (torch.empty(3 * n, dtype=torch.int64, device=dev) for _ in range(4))
+        nm = ctypes.c_uint64(0)
+        mo = L.GsMatchOut(mt.data_ptr(), ms_.data_ptr(), md.data_ptr(), mv.data_ptr(), mi.data_ptr(), 3 * n, ctypes.pointer(nm),
+                          L.GS_MEM_DEVICE, 0)
+        with eng.weighted_matching() as w:     # warm-up: code objects and workspace, on one batch
+            timed(lambda: lib.gs_match_edges(eng.ctx, w.handle, ctypes.byref(mb[0]), ctypes.byref(mo)))
+        res = {}
+        st = eng.weighted_matching((1 << a.scale) + 2 * n)      # no table growth inside the timed calls
+        for name in ("cold", "warm"):
+            rows = []
+            for b, bm in zip(batches, mb):
+                csr = timed(lambda: lib.gs_window_csr(eng.ctx, ctypes.byref(b), ALL, ctypes.byref(cso)))
+                ms = timed(lambda: lib.gs_match_edges(eng.ctx, st.handle, ctypes.byref(bm), ctypes.byref(mo)))
+                info = st.last_batch()
+                rows.append({"ms": round(ms, 3), "edges_per_s": round(n / (ms * 1e-3)), "csr_ms": round(csr, 3),
+                             "ratio_to_csr": round(ms / csr, 2), "rounds": info["rounds"],
+                             "block_iterations": info["block_iterations"],
+                             "pending_after": {str(k): v for k, v in info["pending_after"].items()}, "events": nm.value})
+            total = sum(r["ms"] for r in rows)
+            res[name] = {"per_batch": rows, "ms_stream": round(total, 3), "edges_per_s": round(a.batches * n / (total * 1e-3)),
+                         "ratio_to_csr": round(total / sum(r["csr_ms"] for r in rows), 2)}
+        res["matched_edges"], res["records"], res["total_weight"] = st.size()
+        st.close()
+        # one host thread (the reference's parallelism for this operator) on the same stream
+        root = Path(__file__).resolve().parent
+        exe, cpp = root / "matching_cpu", root / "matching_cpu.cpp"
+        if not exe.exists() or exe.stat().st_mtime < cpp.stat().st_mtime:      # never time a stale binary
+            subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), str(cpp)], check=True)
+        # the stream goes down a pipe, column by column (it prints only after it has read everything)
+        proc = subprocess.Popen([str(exe), "-", str(n), str(a.batches), "2"], stdin=subprocess.PIPE, stdout=subprocess.PIPE)
+        for part in ([s for s, _ in cols], [d for _, d in cols], vals):
+            for t in part:
+                proc.stdin.write(t.cpu().numpy().astype(np.int64).tobytes())
+        proc.stdin.close()
+        text = proc.stdout.read()
+        if proc.wait() != 0:
+            raise RuntimeError(f"matching_cpu ended with status {proc.returncode}")
+        cpu = json.loads(text)
+        for name, p in zip(("cold", "warm"), cpu["passes"]):
+            total = sum(p["ms_per_batch"])
+            if p["events_per_batch"] != [r["events"] for r in res[name]["per_batch"]]:
+                raise RuntimeError(f"matching: the host restatement counts other events on the {name} pass")
+            res[name]["cpu_one_thread"] = {"ms_per_batch": p["ms_per_batch"], "ms_stream": round(total, 3),
+                                           "edges_per_s": round(a.batches * n / (total * 1e-3))}
+            res[name]["gpu_over_cpu_time"] = round(res[name]["ms_stream"] / total, 3)
+            res[name]["faster"] = "gpu" if res[name]["ms_stream"] < total else "one cpu thread"
+        return res
+
     legs = a.legs.split(",")
     out = {"scale": a.scale, "batches": a.batches, "edges_per_batch": n, "records_per_batch": R, "passes": a.passes}
+    if "matching" in legs:
+        out["matching"] = matching_leg()
     if "trisample" in legs:
         out["trisample"] = {}
         for samples in (int(x) for x in a.samples.split(",")):
