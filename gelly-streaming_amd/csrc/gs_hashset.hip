@@ -638,8 +638,9 @@ __global__ __launch_bounds__(256) void k_hs_clist(const uint32_t* __restrict__ c
 
 // One exact java.util.HashMap<Long> per complex vertex (JDK 8+ putVal / resize / treeifyBin /
 // TreeNode.treeify / putTreeVal / balanceInsertion / rotations / moveRootToFront / split / untreeify;
-// the same restatement as the oracle's hashset_order).  Nodes are indexed 0..k-1 in arrival order;
-// the table is resized in place (old bin j feeds new bins j and j + oldCap only).
+// the same restatement as the oracle's hashset_order; tests/jdk_hashmap_ref.py is the independent model
+// both are held to).  Nodes are indexed 0..k-1 in arrival order; the table is resized in place (old bin j
+// feeds new bins j and j + oldCap only).
 struct JNode {
   uint32_t hash;
   int32_t next, prev, parent, left, right;
@@ -651,9 +652,11 @@ struct JMap {
   int32_t* tab;
   uint32_t cap, thr, size, flags;
 };
+// putTreeVal / treeify comparison: Node.hash is a Java int, so a tree bin is ordered by (hash as a SIGNED
+// int, Long value); the stored hash stays uint32_t for the bin masks and is cast here
 __device__ int j_dir(const JMap& m, int32_t p, uint32_t h, int64_t k) {
-  if (m.n[p].hash > h) return -1;
-  if (m.n[p].hash < h) return 1;
+  if ((int32_t)m.n[p].hash > (int32_t)h) return -1;
+  if ((int32_t)m.n[p].hash < (int32_t)h) return 1;
   return k < m.key[p] ? -1 : 1;   // Long.compareTo; keys are distinct
 }
 __device__ int32_t j_rotl(JNode* n, int32_t root, int32_t p) {

@@ -433,12 +433,13 @@ static int cmp_hs(const void* a, const void* b) {
 
 /* The exact java.util.HashMap<Long, Object> of a HashSet<Long> built by add() in arrival order (JDK 8+
  * HashMap.putVal / resize / treeifyBin / TreeNode.treeify / putTreeVal / balanceInsertion / rotateLeft /
- * rotateRight / moveRootToFront / split / untreeify, restated over index-linked nodes):
+ * rotateRight / moveRootToFront / split / untreeify, restated over index-linked nodes; pinned by the
+ * independent object model tests/jdk_hashmap_ref.py and its paper answers):
  *  - a list bin that reaches 9 nodes calls treeifyBin: below capacity 64 that resizes the table instead
  *    (so the final capacity is not a function of the size alone);
- *  - a tree bin keeps its nodes in a red-black tree ordered by (hash, Long value) AND in its `next`
- *    list, which iteration follows: treeify keeps the list order but moves the root to the front; a
- *    later insert goes right after its tree parent, then the (new) root moves to the front;
+ *  - a tree bin keeps its nodes in a red-black tree ordered by (hash as a SIGNED int, Long value) AND in
+ *    its `next` list, which iteration follows: treeify keeps the list order but moves the root to the
+ *    front; a later insert goes right after its tree parent, then the (new) root moves to the front;
  *  - resize splits every bin into lo / hi lists in list order; a tree half of <= 6 nodes becomes a list
  *    again, a larger one is re-treeified (unless the other half is empty).
  * Iteration walks bins 0..cap-1 and follows `next`. */
@@ -459,9 +460,11 @@ static uint32_t j_hash(int64_t x) {
   const uint32_t h = (uint32_t)((uint64_t)x ^ ((uint64_t)x >> 32));
   return h ^ (h >> 16);
 }
-static int j_dir(const jnode* p, uint32_t h, int64_t k) {   /* putTreeVal / treeify comparison */
-  if (p->hash > h) return -1;
-  if (p->hash < h) return 1;
+/* putTreeVal / treeify comparison: Node.hash is a Java int, so `(ph = p.hash) > h` is a SIGNED compare (the
+ * stored hash stays uint32_t for the bin masks; bit 31 of it is bit 31 xor bit 63 of the id) */
+static int j_dir(const jnode* p, uint32_t h, int64_t k) {
+  if ((int32_t)p->hash > (int32_t)h) return -1;
+  if ((int32_t)p->hash < (int32_t)h) return 1;
   return k < p->key ? -1 : 1;   /* Long.compareTo; keys are distinct */
 }
 static int32_t j_rotl(jnode* n, int32_t root, int32_t p) {

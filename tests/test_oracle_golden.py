@@ -92,7 +92,15 @@ def test_hashset_exact_known_answers(oracle):
        to 32, where evens (bucket 0) precede odds (bucket 16), each in insertion order;
      - eight of them stay one plain bin;
      - 64, .., 704: the 9th and 10th adds resize to 32 and 64 (all still bucket 0), the 11th treeifies:
-       ascending inserts give the red-black root 256 (4th key), moveRootToFront puts it first."""
+       ascending inserts give the red-black root 256 (4th key), moveRootToFront puts it first.
+    A tree bin is ordered by (hash as a SIGNED int, Long value); the three sets above have non-negative hashes
+    and cannot tell.  Two more, derived step by step in tests/test_jdk_hashmap_ref.py
+    (test_model_known_answer_bit31_signed / _bit63_signed), can:
+     - (j << 6) | ((j & 1) << 31), j = 1..11: the odd j have negative hashes (bit 31 of the id) and sort first,
+       the red-black root is 128 (the 2nd key) and moves to the front; compared unsigned the root would be the
+       1st key and the order the insertion order;
+     - the same with the sign from bit 63 of the id, then 128 - 2^63 (linked right after its tree parent
+       64 - 2^63, mid-list) and 576 (linked right after 640)."""
     ex, pl, f = oracle.hashset_order([16 * j for j in range(1, 10)])
     assert ex.tolist() == [32, 64, 96, 128, 16, 48, 80, 112, 144] and f == 2
     assert pl.tolist() == [16 * j for j in range(1, 10)]
@@ -100,6 +108,15 @@ def test_hashset_exact_known_answers(oracle):
     assert ex.tolist() == pl.tolist() == [16 * j for j in range(1, 9)] and f == 0
     ex, pl, f = oracle.hashset_order([64 * j for j in range(1, 12)])
     assert ex.tolist() == [256, 64, 128, 192] + [64 * j for j in range(5, 12)] and f == 3
+    ids = [(j << 6) | ((j & 1) << 31) for j in range(1, 12)]
+    ex, pl, f = oracle.hashset_order(ids)
+    assert ex.tolist() == [128, 2147483712, 2147483840, 256, 2147483968, 384, 2147484096, 512, 2147484224, 640,
+                           2147484352] and f == 3
+    assert pl.tolist() == ids
+    T = 1 << 63
+    ex, pl, f = oracle.hashset_order([(j << 6) - ((j & 1) << 63) for j in range(1, 12)] + [128 - T, 576])
+    assert ex.tolist() == [128, 64 - T, 128 - T, 192 - T, 256, 320 - T, 384, 448 - T, 512, 576 - T, 640, 576,
+                           704 - T] and f == 3
 
 
 def test_hashset_exact_matches_plain_without_collisions(oracle):
