@@ -11,8 +11,8 @@ The directory name contains a hyphen, so it is loaded by path:
 or with ``load_package()`` from __graft_entry__.py.
 """
 from ._lib import GsError, load as load_library  # noqa: F401
-from .engine import (CommGroup, ContinuousState, DistinctState, Engine, StageTimes, TriangleSamplerState,  # noqa: F401
-                     WeightedMatchingState)
+from .engine import (AssignComponentsState, CommGroup, ContinuousState, DistinctState, Engine, StageTimes,  # noqa: F401
+                     TriangleSamplerState, WeightedMatchingState)
 from .functions import (Collector, CountFold, CountReduce, DegreeMaxNeighborFold, EdgesApply, EdgesFold,  # noqa: F401
                         EdgesReduce, MaxReduce, MaxValuesFold, MinReduce, MinValuesFold, SumReduce, SumValuesFold)
 from .stream import (AscendingTimestampExtractor, DataStream, EdgeColumns, EdgeDirection,  # noqa: F401
@@ -22,6 +22,7 @@ from .triangles import CountTriangles, GenerateCandidateEdges, window_triangles 
 from .triangle_estimate import (TriangleSummer, broadcast_triangle_count,  # noqa: F401
                                 incidence_sampling_triangle_count)
 from .matching import MatchingEvent, centralized_weighted_matching  # noqa: F401
+from .iterative_cc import AssignComponents, IterativeConnectedComponents  # noqa: F401
 from .aggregation import BipartitenessCheck, Candidates, ConnectedComponents, WindowGraphAggregation  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

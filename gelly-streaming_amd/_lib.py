@@ -60,7 +60,9 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_trisample_create", "gs_trisample_destroy", "gs_trisample_edges", "gs_trisample_size",
            "gs_trisample_export", "gs_trisample_import",
            "gs_match_create", "gs_match_destroy", "gs_match_edges", "gs_match_size", "gs_match_capacity",
-           "gs_match_last_batch", "gs_match_export", "gs_match_import")
+           "gs_match_last_batch", "gs_match_export", "gs_match_import",
+           "gs_assign_create", "gs_assign_destroy", "gs_assign_edges", "gs_assign_size", "gs_assign_capacity",
+           "gs_assign_last_batch", "gs_assign_export", "gs_assign_import")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -98,6 +100,11 @@ class GsEdgeOut(ctypes.Structure):   # gs_edge_out: the edges gs_distinct_edges 
 class GsMatchOut(ctypes.Structure):   # gs_match_out: the MatchingEvents gs_match_edges emits
     _fields_ = [("type", P), ("src", P), ("dst", P), ("val", P), ("index", P), ("capacity", u64),
                 ("n_out", ctypes.POINTER(u64)), ("mem", i32), ("reserved", i32)]
+
+
+class GsAssignOut(ctypes.Structure):   # gs_assign_out: the (vertex, label) records gs_assign_edges emits
+    _fields_ = [("vertex", P), ("label", P), ("edge", P), ("capacity", u64), ("n_out", ctypes.POINTER(u64)), ("mem", i32),
+                ("reserved", i32)]
 
 
 class GsTrisampleHeader(ctypes.Structure):   # gs_trisample_header: a sampler checkpoint's parameters and counters
@@ -306,6 +313,14 @@ def load() -> ctypes.CDLL:
         "gs_match_last_batch": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "gs_match_export": (st, [P, P, ctypes.POINTER(GsEdgeOut)]),
         "gs_match_import": (st, [P, P, ctypes.POINTER(GsEdgeBatch)]),
+        "gs_assign_create": (st, [P, u64, ctypes.POINTER(P)]),
+        "gs_assign_destroy": (None, [P]),
+        "gs_assign_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsAssignOut)]),
+        "gs_assign_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_assign_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_assign_last_batch": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_assign_export": (st, [P, P, ctypes.POINTER(GsVertexOut)]),
+        "gs_assign_import": (st, [P, P, ctypes.POINTER(GsPartialBatch)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)

@@ -105,8 +105,10 @@ struct gs_ctx {
   gs::DevBuf cc[4];              // union-find aggregations (gs_cc_common.hpp; [3]: the signed state's signs)
   gs::DevBuf ct[5];              // continuous streams (gs_continuous.hip): run keys, offsets, bases, flags, scan;
                                  // gs_distinct.hip: [0] held slots, [3] keep flags, [4] their scan
+                                 // gs_assign.hip: [0] edge keys of the second sort, [1] / [2] record numbers
   gs::DevBuf ts[12];             // sampling triangle estimators (gs_trisample.hip): epochs, wanted table, events;
                                  // gs_matching.hip: per-edge slots, pending lists, footprints, event scratch
+                                 // gs_assign.hip: per-edge slots, roots, live lists, losers; record scratch; [11] growth map
   uint32_t tri_guess_B = 0;      // triangles: the previous window's id width (its partition histograms ride the id scan)
   uint32_t tri_B = 0;            // split-window triangles: id geometry of the current window
   uint64_t tri_key_xor = 0;

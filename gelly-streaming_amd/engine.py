@@ -103,7 +103,7 @@ def _out_dtypes():
         import torch
 
         _OUT_DTYPES = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32,
-                       np.float64: torch.float64, np.uint8: torch.uint8}
+                       np.float64: torch.float64, np.uint8: torch.uint8, np.uint32: torch.uint32}
     return _OUT_DTYPES
 
 
@@ -698,6 +698,12 @@ class Engine:
         of one batch."""
         return WeightedMatchingState(self, reserve_vertices)
 
+    def assign_components(self, reserve_vertices: int = 0) -> "AssignComponentsState":
+        """gs_assign_create: an empty device-resident partition for example/IterativeConnectedComponents' AssignComponents
+        mapper (parallelism 1): per batch of edges, one (vertex, label) record per vertex whose component label
+        changes.  reserve_vertices: the vertices expected plus two per edge of one batch."""
+        return AssignComponentsState(self, reserve_vertices)
+
     def triangle_sampler(self, mode: str, samples: int, vertex_count: int, seed: int = 0,
                          first_sampler: int = 0) -> "TriangleSamplerState":
         """gs_trisample_create: the samplers of one TriangleSampler subtask of BroadcastTriangleCount
@@ -1194,6 +1200,112 @@ class WeightedMatchingState:
         share an endpoint are refused)."""
         b, keep, dev = self.engine._batch(src, dst, val)
         self.engine._check(self._L.gs_match_import(self.engine.ctx, self.handle, ctypes.byref(b)))
+
+
+class AssignComponentsState:
+    """gs_assign: the partition of one AssignComponents mapper (include/gelly_hip.h, "AssignComponents") -- per
+    vertex the smallest vertex of its component, in HBM across calls.  Feed it the stream in batches of any size:
+    the concatenated records depend only on the stream.  Columns are numpy arrays (results come back as numpy) or
+    CUDA tensors of the engine's device (results stay in HBM)."""
+
+    _DTYPES = (np.int64, np.int64, np.uint32)
+
+    def __init__(self, engine: Engine, reserve_vertices: int = 0):
+        self.engine = engine
+        self._L = engine._L
+        h = ctypes.c_void_p()
+        engine._check(self._L.gs_assign_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
+        self.handle = h
+        self.last_records = 0
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.gs_assign_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def edges(self, src, dst, out=None, capacity: int = None):
+        """gs_assign_edges: the records of the batch as (vertex, label, edge), grouped by edge in arrival order
+        and ascending by vertex inside one edge; edge (uint32) is the position inside the batch of the edge that
+        caused the record.  out: optional (vertex, label, edge) device tensors (int64, int64, uint32), reused
+        across batches; the shortest one's length is the capacity.  capacity: room for that many records
+        (default: two per edge; a batch that emits more -- a merge emits a whole component -- runs again with the
+        number it reported: a call that fails leaves the state as it was).  With out or capacity given, a batch
+        that does not fit raises GsError(GS_ECAPACITY), last_records holding the number needed."""
+        e = self.engine
+        b, keep, dev = e._batch(src, dst, None)
+        if out is not None:
+            e._check_out(out, dev, self._DTYPES)
+            cap = min(t.numel() for t in out)
+            if capacity is not None:
+                cap = min(cap, int(capacity))
+        else:
+            cap = int(2 * b.n if capacity is None else capacity)
+        retry = out is None and capacity is None
+        for _ in range(2):
+            cols = list(out) if out is not None else [e._empty(dev, cap, d) for d in self._DTYPES]
+            n_out = ctypes.c_uint64(0)
+            ao = L.GsAssignOut(*[_ptr(t) for t in cols], cap, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+            st = self._L.gs_assign_edges(e.ctx, self.handle, ctypes.byref(b), ctypes.byref(ao))
+            if st != L.GS_ECAPACITY or not retry:
+                break
+            cap = n_out.value
+        self.last_records = n_out.value
+        e._check(st)
+        k = n_out.value
+        return tuple(t[:k] for t in cols)
+
+    def size(self):
+        """gs_assign_size: (vertices, components, records emitted so far)."""
+        v, c, r = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_assign_size(self.handle, ctypes.byref(v), ctypes.byref(c), ctypes.byref(r)))
+        return v.value, c.value, r.value
+
+    def capacity(self):
+        """gs_assign_capacity: (slots of the vertex table, doublings so far)."""
+        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(self._L.gs_assign_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
+        return s.value, g.value
+
+    def last_batch(self):
+        """gs_assign_last_batch: {rounds, merging_edges, records, live_after: {1, 2, 4, 8: edges}} of the last batch."""
+        r, m, k, la = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), (ctypes.c_uint64 * 4)()
+        self.engine._check(self._L.gs_assign_last_batch(self.handle, ctypes.byref(r), ctypes.byref(m), ctypes.byref(k), la))
+        return {"rounds": r.value, "merging_edges": m.value, "records": k.value, "live_after": {1 << i: la[i] for i in range(4)}}
+
+    def export(self, device: bool = False):
+        """gs_assign_export: the checkpoint (vertices ascending, labels) -- the format of Engine.components' output;
+        numpy or (device=True) CUDA tensors."""
+        e = self.engine
+        V = self.size()[0]
+        keys, vals = e._empty(device, V, np.int64), e._empty(device, V, np.int64)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(_ptr(keys), _ptr(vals), V, ctypes.pointer(n_out), L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_assign_export(e.ctx, self.handle, ctypes.byref(vo)))
+        n = n_out.value
+        return keys[:n], vals[:n]
+
+    def load(self, vertices, labels):
+        """gs_assign_import: restore a checkpoint, or an Engine.components output, into this, still empty, state."""
+        if _is_torch(vertices):
+            import torch
+
+            vertices, labels = vertices.to(torch.int64).contiguous(), labels.to(torch.int64).contiguous()
+        else:
+            labels = np.ascontiguousarray(labels, dtype=np.int64)
+        pb, keep, dev = self.engine._partial_batch(vertices, labels)
+        self.engine._check(self._L.gs_assign_import(self.engine.ctx, self.handle, ctypes.byref(pb)))
 
 
 class TriangleSamplerState:

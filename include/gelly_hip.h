@@ -728,6 +728,75 @@ GS_API gs_status gs_match_export(gs_ctx* ctx, const gs_match* state, gs_edge_out
  * number of rows. */
 GS_API gs_status gs_match_import(gs_ctx* ctx, gs_match* state, const gs_edge_batch* rows);
 
+/* ---- AssignComponents: a device-resident component-label change stream ---------------------------- */
+/* example/IterativeConnectedComponents.java:67-168: the AssignComponents mapper keeps the partition of the
+ * vertices seen so far and emits one (vertex, componentId) record per vertex whose component id changes; the
+ * id is always the smallest vertex of the component (signed comparison, as Math.min and >= do).  A gs_assign
+ * holds that partition in HBM across calls.  For an arriving edge (s, t):
+ *   both unknown (also s == t)            (s, m), (t, m) with m = min(s, t), in this order; a self-loop on an
+ *                                         unknown vertex emits (v, v) twice
+ *   one known in component c, the other   (x, c); x joins c
+ *     x unknown, x > c
+ *   one known in c, x unknown, x < c      (v, x) for every vertex v of the component, ascending by vertex, not
+ *                                         for x itself; the component is relabelled x and x joins
+ *   both known, labels a != b             (v, min(a, b)) for every vertex of the component with the larger
+ *                                         label, ascending by vertex; the two merge
+ *   both known, same label                nothing
+ * Where this deviates from the reference, and why:
+ *   - addToExistingComponent :136-139 emits a vertex x that joins a component with a smaller id but never adds
+ *     it to the set, so x's own record, returning over the feedback edge, finds x unknown and is emitted again,
+ *     for ever: the literal mapper has no finite output.  This library builds the reading of the mapper's
+ *     comments ("add the target to the source's component"): x joins.  Under it a fed-back record (v, c) has both
+ *     ends in one component and changes nothing, so the output is a function of the edge stream alone.
+ *   - inside one edge's emission the reference follows HashSet iteration order; here the order is canonical,
+ *     ascending by vertex (the two records of a new component: src, then dst).
+ *   - the reference uses -1 as its "no component" marker, so its behaviour with a vertex -1 is an accident; here
+ *     every int64 is a legal id and -1 is an ordinary vertex.
+ *   - parallelism 1 only: at parallelism P the reference's subtasks exchange state through the feedback edge,
+ *     whose timing decides the output.
+ * The stream is fed in batches of any size; the concatenated records depend only on the stream, never on where
+ * it was cut.  One state is used from one thread at a time, with a ctx of its device.  A call that returns an
+ * error leaves the state exactly as it was.  A batch holds at most 2^32 - 1 edges.  Outputs are complete on
+ * return (host memory) or in the order of the ctx's stream (device memory). */
+typedef struct gs_assign gs_assign;
+/* Record output: the k-th record of the batch in row k, grouped by edge in arrival order.  Each of the three
+ * columns may be NULL, and a NULL column is not written.  edge[k] is the position inside this batch of the edge
+ * that caused record k. */
+typedef struct gs_assign_out {
+  int64_t* vertex;         /* [capacity] or NULL                                           */
+  int64_t* label;          /* [capacity] or NULL                                           */
+  uint32_t* edge;          /* [capacity] or NULL                                           */
+  uint64_t capacity;
+  uint64_t* n_out;         /* host pointer: records written / needed                       */
+  int32_t mem;             /* gs_mem of the three columns                                  */
+  int32_t reserved;
+} gs_assign_out;
+/* An empty state with room for reserve_vertices vertices before its first growth (0 = smallest).  A batch of n
+ * edges needs room for the vertices seen so far + 2n before it runs. */
+GS_API gs_status gs_assign_create(gs_ctx* ctx, uint64_t reserve_vertices, gs_assign** out);
+GS_API void gs_assign_destroy(gs_assign* state);
+/* One batch of the stream (batch->val is ignored).  The number of records R depends on the data and may exceed
+ * 2n by far (a merge emits a whole component); it is counted in 64 bits.  capacity < R, when a column is asked
+ * for: GS_ECAPACITY with *n_out = R and the state unchanged.  R >= 2^32: GS_EUNSUPPORTED (split the batch).  With
+ * all three columns NULL the call only updates the state and reports R. */
+GS_API gs_status gs_assign_edges(gs_ctx* ctx, gs_assign* state, const gs_edge_batch* batch, gs_assign_out* out);
+/* Vertices and components of the state, and the records emitted so far (each pointer may be NULL). */
+GS_API gs_status gs_assign_size(const gs_assign* state, uint64_t* vertices, uint64_t* components, uint64_t* records);
+/* The vertex table's slots and how often it has doubled (either pointer may be NULL). */
+GS_API gs_status gs_assign_capacity(const gs_assign* state, uint64_t* slots, uint64_t* growths);
+/* How the last gs_assign_edges call went (each pointer may be NULL): its rounds, the edges that merged two
+ * components, its records, and the edges still live after rounds 1, 2, 4 and 8 (live_after[4]; 0 for a round it
+ * did not need). */
+GS_API gs_status gs_assign_last_batch(const gs_assign* state, uint64_t* rounds, uint64_t* merging_edges, uint64_t* records,
+                                      uint64_t* live_after);
+/* Checkpoint: (vertex, label) rows ascending by vertex, vals I64 -- the format of a gs_window_components
+ * output.  capacity < the vertices: GS_ECAPACITY with *n_out = their number. */
+GS_API gs_status gs_assign_export(gs_ctx* ctx, const gs_assign* state, gs_vertex_out* out);
+/* Restore a checkpoint, or a gs_window_components output, into an EMPTY state (GS_EINVAL otherwise): keys =
+ * vertices, vals = I64 labels, rows in any order.  GS_EINVAL, the state unchanged, unless every vertex has one
+ * row, label <= vertex, and the label's own row has label == vertex.  The record count starts at 0. */
+GS_API gs_status gs_assign_import(gs_ctx* ctx, gs_assign* state, const gs_partial_batch* rows);
+
 /* Candidate records of one window as produced by GenerateCandidateEdges (gs_pair_out layout). */
 typedef struct gs_pair_batch {
   const int64_t* a;

@@ -9,6 +9,11 @@ The `matching` leg: gs_match_edges (all five event columns out, room for 3n even
 16-bit values, a cold state and then a second pass of the same stream over the warm state -- per batch ms,
 edges/s, rounds, blocking iterations, edges pending after rounds 1, 2, 4 and 8, events, and the ratio to
 gs_window_csr -- next to one host thread running tools/matching_cpu.cpp on the same stream.
+The `assign` leg: gs_assign_edges (vertex, label and edge columns out) on the same batches, a cold state and then
+a second pass of the same stream over the warm state, --passes times over; per batch the median ms, edges/s,
+rounds, records and the edges live after rounds 1, 2, 4 and 8.  In the same process, alternating batch by batch:
+gs_window_components on the batch with the previous call's output fed back as `prev` (the way to the same
+information today: it re-emits every vertex) and gs_window_csr; and one host thread running tools/assign_cpu.cpp.
 
     python tools/time_continuous.py [--scale 22] [--batches 8] [--log2-batch 22] [--passes 3]"""
 import argparse
@@ -156,10 +161,117 @@ def main():
             res[name]["faster"] = "gpu" if res[name]["ms_stream"] < total else "one cpu thread"
         return res
 
+    def assign_leg():
+        """cold and warm passes of gs_assign_edges next to gs_window_components with its state fed back and
+        gs_window_csr, alternating batch by batch; medians over a.passes repetitions; one host thread"""
+        import numpy as np
+
+        room = [2 * n]      # records per batch depend on the data: the columns grow when a call asks for more
+        cols_out = []
+        na = ctypes.c_uint64(0)
+
+        def columns():
+            cols_out[:] = [torch.empty(room[0], dtype=torch.int64, device=dev), torch.empty(room[0], dtype=torch.int64, device=dev),
+                           torch.empty(room[0], dtype=torch.uint32, device=dev)]
+            return L.GsAssignOut(cols_out[0].data_ptr(), cols_out[1].data_ptr(), cols_out[2].data_ptr(), room[0],
+                                 ctypes.pointer(na), L.GS_MEM_DEVICE, 0)
+
+        ao = [columns()]
+
+        def assign_call(st, b):
+            """the batch's ms; a call that asks for more room changes nothing and is timed again with it"""
+            for _ in range(2):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                status = lib.gs_assign_edges(eng.ctx, st.handle, ctypes.byref(b), ctypes.byref(ao[0]))
+                e1.record()
+                e1.synchronize()
+                if status != L.GS_ECAPACITY:
+                    break
+                room[0] = na.value + na.value // 8
+                ao[0] = columns()
+            if status != L.GS_OK:
+                raise pkg.GsError(status, lib.gs_last_error(eng.ctx).decode())
+            return e0.elapsed_time(e1)
+
+        V = 1 << a.scale
+        pk = [torch.empty(V + 2 * n + 1, dtype=torch.int64, device=dev) for _ in range(4)]   # components: prev / out, ping-pong
+        ncc = ctypes.c_uint64(0)
+
+        def one_run():
+            st = eng.assign_components(V + 2 * n)      # no table growth inside the timed calls
+            res, m, flip = {}, 0, 0
+            for name in ("cold", "warm"):
+                rows = []
+                for b in batches:
+                    csr = timed(lambda: lib.gs_window_csr(eng.ctx, ctypes.byref(b), ALL, ctypes.byref(cso)))
+                    prev = L.GsPartialBatch(pk[flip].data_ptr(), pk[flip + 1].data_ptr(), None, m, L.GS_I64, L.GS_MEM_DEVICE)
+                    co_ = L.GsVertexOut(pk[2 - flip].data_ptr(), pk[3 - flip].data_ptr(), V + 2 * n + 1, ctypes.pointer(ncc),
+                                        L.GS_MEM_DEVICE, 0)
+                    cc = timed(lambda: lib.gs_window_components(eng.ctx, ctypes.byref(b), ctypes.byref(prev) if m else None,
+                                                                ctypes.byref(co_)))
+                    m, flip = ncc.value, 2 - flip
+                    ms = assign_call(st, b)
+                    info = st.last_batch()
+                    rows.append({"ms": ms, "csr_ms": csr, "components_ms": cc, "rounds": info["rounds"],
+                                 "merging_edges": info["merging_edges"], "records": info["records"],
+                                 "live_after": {str(k): v for k, v in info["live_after"].items()}})
+                res[name] = rows
+            size = st.size()
+            if size[0] != m:
+                raise RuntimeError(f"assign: {size[0]} vertices, gs_window_components kept {m}")
+            st.close()
+            return res, size
+
+        with eng.assign_components() as w:     # warm-up: code objects and workspace, on one batch
+            assign_call(w, batches[0])
+        one_run()
+        runs = [one_run() for _ in range(a.passes)]
+        res = {}
+        for name in ("cold", "warm"):
+            rows = []
+            for i in range(a.batches):
+                r = dict(runs[-1][0][name][i])
+                for k in ("ms", "csr_ms", "components_ms"):
+                    r[k] = round(statistics.median(run[0][name][i][k] for run in runs), 3)
+                r["edges_per_s"] = round(n / (r["ms"] * 1e-3))
+                r["ratio_to_components"] = round(r["ms"] / r["components_ms"], 3)
+                rows.append(r)
+            tot = {k: sum(r[k] for r in rows) for k in ("ms", "csr_ms", "components_ms")}
+            res[name] = {"per_batch": rows, "ms_stream": round(tot["ms"], 3), "components_ms_stream": round(tot["components_ms"], 3),
+                         "csr_ms_stream": round(tot["csr_ms"], 3), "edges_per_s": round(a.batches * n / (tot["ms"] * 1e-3)),
+                         "ratio_to_components": round(tot["ms"] / tot["components_ms"], 3),
+                         "ratio_to_csr": round(tot["ms"] / tot["csr_ms"], 3)}
+        res["vertices"], res["components"], res["records"] = runs[-1][1]
+        # one host thread (the reference's parallelism for this operator) on the same stream
+        root = Path(__file__).resolve().parent
+        exe, cpp = root / "assign_cpu", root / "assign_cpu.cpp"
+        if not exe.exists() or exe.stat().st_mtime < cpp.stat().st_mtime:      # never time a stale binary
+            subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), str(cpp)], check=True)
+        proc = subprocess.Popen([str(exe), "-", str(n), str(a.batches), "2"], stdin=subprocess.PIPE, stdout=subprocess.PIPE)
+        for part in ([s for s, _ in cols], [d for _, d in cols]):
+            for t in part:
+                proc.stdin.write(t.cpu().numpy().astype(np.int64).tobytes())
+        proc.stdin.close()
+        text = proc.stdout.read()
+        if proc.wait() != 0:
+            raise RuntimeError(f"assign_cpu ended with status {proc.returncode}")
+        cpu = json.loads(text)
+        for name, p in zip(("cold", "warm"), cpu["passes"]):
+            total = sum(p["ms_per_batch"])
+            if p["records_per_batch"] != [r["records"] for r in res[name]["per_batch"]]:
+                raise RuntimeError(f"assign: the host restatement counts other records on the {name} pass")
+            res[name]["cpu_one_thread"] = {"ms_per_batch": p["ms_per_batch"], "ms_stream": round(total, 3),
+                                           "edges_per_s": round(a.batches * n / (total * 1e-3))}
+            res[name]["gpu_over_cpu_time"] = round(res[name]["ms_stream"] / total, 3)
+        return res
+
     legs = a.legs.split(",")
     out = {"scale": a.scale, "batches": a.batches, "edges_per_batch": n, "records_per_batch": R, "passes": a.passes}
     if "matching" in legs:
         out["matching"] = matching_leg()
+    if "assign" in legs:
+        out["assign"] = assign_leg()
     if "trisample" in legs:
         out["trisample"] = {}
         for samples in (int(x) for x in a.samples.split(",")):
