@@ -38,12 +38,10 @@
 //                 records per slot; after the scan the same walk writes them, and the new labels -- the only
 //                 kernel of a batch that changes the state, and it runs after every check that can refuse the call
 //   sort          by the order key inside an edge (skipped when every edge emitted one record), then stably by edge
-#include "gs_ops.hpp"
+#include "gs_table.hpp"
 
 namespace gs {
 
-constexpr unsigned long long AS_EMPTY = ~0ull;
-constexpr unsigned long long AS_SIGN = 1ull << 63;
 constexpr uint32_t AS_NONE = 0xFFFFFFFFu;
 // u64 words of gs_assign::meta
 enum { AS_ERR = 0, AS_CLAIM = 1, AS_PEND = 2, AS_FIN = 3, AS_NEW = 4, AS_RETIRED = 5, AS_LOOPS = 6, AS_DUMP = 7, AS_ROOTS = 8,
@@ -70,47 +68,18 @@ struct AsTable {
   unsigned long long* meta;
 };
 
-// the slot of `id`, claimed if absent (*fresh); AS_NONE when the table is full (not reached at load <= 1/2)
+// the slot of `id`, claimed if absent (*fresh); vertex -1: the side slot, never fresh; AS_NONE (what tab_claim's
+// ~0 narrows to: slots stay below 2^31) when the table is full
 __device__ __forceinline__ uint32_t as_slot(const AsTable& t, unsigned long long id, bool* fresh) {
   *fresh = false;
-  if (id == AS_EMPTY) return (uint32_t)(t.mask + 1);
-  unsigned long long s = ct_hash(id) & t.mask;
-  for (unsigned long long i = 0; i <= t.mask; ++i, s = (s + 1) & t.mask) {
-    unsigned long long k = __hip_atomic_load(&t.slots[s].id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == AS_EMPTY) {
-      k = atomicCAS(&t.slots[s].id, AS_EMPTY, id);
-      if (k == AS_EMPTY) {
-        *fresh = true;
-        return (uint32_t)s;
-      }
-    }
-    if (k == id) return (uint32_t)s;
-  }
-  return AS_NONE;
+  if (id == TAB_EMPTY) return (uint32_t)(t.mask + 1);
+  return (uint32_t)tab_claim<sizeof(AsSlot) / 8>(&t.slots->id, t.mask, id, fresh);
 }
 
 // the slot of `id` if the table holds it, else AS_NONE (claims nothing)
 __device__ __forceinline__ uint32_t as_lookup(const AsTable& t, unsigned long long id) {
-  if (id == AS_EMPTY) return (uint32_t)(t.mask + 1);
-  unsigned long long s = ct_hash(id) & t.mask;
-  for (unsigned long long i = 0; i <= t.mask; ++i, s = (s + 1) & t.mask) {
-    const unsigned long long k = t.slots[s].id;
-    if (k == id) return (uint32_t)s;
-    if (k == AS_EMPTY) return AS_NONE;
-  }
-  return AS_NONE;
-}
-
-// *word += the block's sum of v (every thread of the 256-thread block calls it, once per word and kernel)
-__device__ __forceinline__ void as_block_add(unsigned long long* word, unsigned long long v, unsigned long long* s_part) {
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    if (tot) atomicAdd(word, tot);
-  }
-  __syncthreads();
+  if (id == TAB_EMPTY) return (uint32_t)(t.mask + 1);
+  return (uint32_t)tab_lookup<sizeof(AsSlot) / 8>(&t.slots->id, t.mask, id);
 }
 
 __device__ __forceinline__ unsigned long long as_word(uint32_t round, uint32_t i) {
@@ -131,7 +100,7 @@ __device__ __forceinline__ uint32_t as_find(uint32_t* parent, uint32_t x) {
 // every slot free and outside the state; the side slot's id is vertex -1 from the start
 __global__ __launch_bounds__(256) void k_as_clear(AsSlot* __restrict__ slots, uint32_t* __restrict__ lslot, uint64_t cap) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= cap; s += (uint64_t)gridDim.x * 256) {
-    slots[s] = AsSlot{AS_EMPTY, 0ll};
+    slots[s] = AsSlot{TAB_EMPTY, 0ll};
     lslot[s] = AS_NONE;
   }
 }
@@ -140,7 +109,7 @@ __global__ __launch_bounds__(256) void k_as_clear(AsSlot* __restrict__ slots, ui
 __global__ __launch_bounds__(256) void k_as_insert(AsTable t, const int64_t* __restrict__ bs, const int64_t* __restrict__ bd,
                                                    uint64_t n, uint32_t* __restrict__ va, uint32_t* __restrict__ vb,
                                                    uint32_t* __restrict__ live, uint32_t* __restrict__ loser) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long claims = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     bool fa, fb;
@@ -156,7 +125,7 @@ __global__ __launch_bounds__(256) void k_as_insert(AsTable t, const int64_t* __r
     if (live) live[i] = (uint32_t)i;
     if (loser) loser[i] = AS_NONE;
   }
-  as_block_add(&t.meta[AS_CLAIM], claims, s_part);
+  block_add(&t.meta[AS_CLAIM], claims, s_part);
 }
 
 // lane per edge: the nodes of its endpoints -- a vertex outside the state is a new singleton (its own slot) and
@@ -200,13 +169,8 @@ __global__ __launch_bounds__(256) void k_as_find(AsTable t, const uint32_t* __re
         stay = true;
       }
     }
-    const unsigned long long m = __ballot(stay);
-    if (!m) continue;
-    const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&t.meta[AS_PEND], (unsigned long long)__popcll(m));
-    base = __shfl(base, leader);
-    if (stay) next[base + __popcll(m & ((1ull << lane) - 1))] = i;
+    const unsigned long long k = wave_compact_base(stay, &t.meta[AS_PEND]);
+    if (stay) next[k] = i;
   }
 }
 
@@ -214,7 +178,7 @@ __global__ __launch_bounds__(256) void k_as_find(AsTable t, const uint32_t* __re
 __global__ __launch_bounds__(256) void k_as_decide(AsTable t, const uint32_t* __restrict__ live, uint32_t cnt, uint32_t round,
                                                    const uint32_t* __restrict__ ra, const uint32_t* __restrict__ rb,
                                                    uint32_t* __restrict__ loser) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   const uint64_t have = min((unsigned long long)cnt, t.meta[AS_PEND]);
   unsigned long long fin = 0;
   for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < have; p += (uint64_t)gridDim.x * 256) {
@@ -241,7 +205,7 @@ __global__ __launch_bounds__(256) void k_as_decide(AsTable t, const uint32_t* __
     loser[i] = lo;
     ++fin;
   }
-  as_block_add(&t.meta[AS_FIN], fin, s_part);
+  block_add(&t.meta[AS_FIN], fin, s_part);
 }
 
 // lane per edge that retired a label: the label its winner side held at that time
@@ -274,7 +238,7 @@ struct AsRec {
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_as_records(AsTable t, const int64_t* __restrict__ bs, const int64_t* __restrict__ bd,
                                                     const uint32_t* __restrict__ va, const uint32_t* __restrict__ vb, AsRec rec) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   const uint64_t cap = t.mask + 1;
   unsigned long long n_new = 0, n_retired = 0, n_loops = 0;
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= cap; s += (uint64_t)gridDim.x * 256) {
@@ -324,7 +288,7 @@ __global__ __launch_bounds__(256) void k_as_records(AsTable t, const int64_t* __
         const uint32_t l = t.plabel[mu];
         if (write) {
           rec.edge[k] = r;
-          rec.key[k] = (pair && r == f) ? (pair_second ? 1ull : 0ull) : ((unsigned long long)id ^ AS_SIGN);
+          rec.key[k] = (pair && r == f) ? (pair_second ? 1ull : 0ull) : ((unsigned long long)id ^ TAB_SIGN);
           rec.vertex[k] = id;
           rec.label[k] = (long long)t.slots[l].id;
           rec.iota[k] = (uint32_t)k;
@@ -339,9 +303,9 @@ __global__ __launch_bounds__(256) void k_as_records(AsTable t, const int64_t* __
     }
   }
   if (COUNT) {
-    as_block_add(&t.meta[AS_NEW], n_new, s_part);
-    as_block_add(&t.meta[AS_RETIRED], n_retired, s_part);
-    as_block_add(&t.meta[AS_LOOPS], n_loops, s_part);
+    block_add(&t.meta[AS_NEW], n_new, s_part);
+    block_add(&t.meta[AS_RETIRED], n_retired, s_part);
+    block_add(&t.meta[AS_LOOPS], n_loops, s_part);
   }
 }
 
@@ -398,25 +362,12 @@ __global__ __launch_bounds__(256) void k_as_dump(AsTable t, unsigned long long* 
   for (uint64_t s0 = (uint64_t)blockIdx.x * 256; s0 <= cap; s0 += (uint64_t)gridDim.x * 256) {
     const uint64_t s = s0 + threadIdx.x;
     const bool occ = s <= cap && t.lslot[s] != AS_NONE;
-    const unsigned long long m = __ballot(occ);
-    if (!m) continue;
-    const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)m) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&t.meta[AS_DUMP], (unsigned long long)__popcll(m));
-    base = __shfl(base, leader);
-    const unsigned long long k = base + __popcll(m & ((1ull << lane) - 1));
+    const unsigned long long k = wave_compact_base(occ, &t.meta[AS_DUMP]);
     if (occ && k < V) {
-      keys[k] = t.slots[s].id ^ AS_SIGN;
+      keys[k] = t.slots[s].id ^ TAB_SIGN;
       labels[k] = t.slots[s].label;
     }
   }
-}
-
-// the sorted checkpoint keys back to int64 ids
-template <typename K>
-__global__ __launch_bounds__(256) void k_as_unkey(const K* __restrict__ sk, uint64_t key_xor, uint64_t n, int64_t* __restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-    out[i] = (int64_t)(((uint64_t)sk[i] ^ key_xor) ^ AS_SIGN);
 }
 
 // restore, step 1: row i marks its vertex's slot (first[] = the smallest row of the vertex)
@@ -445,7 +396,7 @@ __global__ __launch_bounds__(256) void k_as_import_check(AsTable t, uint64_t n, 
 }
 __global__ __launch_bounds__(256) void k_as_import_write(AsTable t, uint64_t n, const int64_t* __restrict__ labels,
                                                          const uint32_t* __restrict__ va, const uint32_t* __restrict__ ls) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long roots = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     const uint32_t s = va[i];
@@ -453,7 +404,7 @@ __global__ __launch_bounds__(256) void k_as_import_write(AsTable t, uint64_t n, 
     t.lslot[s] = ls[i];
     roots += ls[i] == s;
   }
-  as_block_add(&t.meta[AS_ROOTS], roots, s_part);
+  block_add(&t.meta[AS_ROOTS], roots, s_part);
 }
 
 }  // namespace gs
@@ -475,9 +426,6 @@ struct gs_assign {
 namespace {
 
 constexpr uint64_t AS_MAX_CAP = 1ull << 31;   // slot numbers are 32-bit, AS_NONE is none of them
-
-unsigned as_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
-unsigned as_grid_tab(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048)); }
 
 size_t as_round(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -509,7 +457,7 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, unsigned long long* meta, char** 
   t->first = (uint32_t*)take(m * 4);
   t->mask = cap - 1;
   t->meta = meta;
-  hipLaunchKernelGGL(k_as_clear, dim3(as_grid(cap + 1)), dim3(256), 0, c->stream, t->slots, t->lslot, cap);
+  hipLaunchKernelGGL(k_as_clear, dim3(tab_grid(cap + 1)), dim3(256), 0, c->stream, t->slots, t->lslot, cap);
   const gs_status st = hip_check(c, hipGetLastError(), "k_as_clear");
   if (st != GS_OK) {
     hipFree(*block);
@@ -518,23 +466,14 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, unsigned long long* meta, char** 
   return st;
 }
 
-// the state's device words -> host_small[8 .. 8 + AS_META), and a wait for the stream
-gs_status read_meta(gs_ctx* c, const gs_assign* t) {
-  GS_HIP(hipMemcpyAsync(c->host_small + 8, t->meta, AS_META * 8, hipMemcpyDeviceToHost, c->stream));
-  return host_wait(c);
-}
-
 // room for `need` claimed slots at load <= 1/2: grow by doubling (allocate, re-insert the state's vertices,
 // swap).  On any failure the old table stays as it was.
 gs_status reserve(gs_ctx* c, gs_assign* t, uint64_t need) {
   if (need <= t->cap / 2) return GS_OK;
   need = need - t->occupied + t->vertices;   // the re-insert leaves the vertices outside the state behind
-  uint64_t cap = t->cap, doublings = 0;
-  while (need > cap / 2) {
-    if (cap >= AS_MAX_CAP) return set_error(c, GS_ENOMEM, "assign state: %llu vertices", (unsigned long long)need);
-    cap *= 2;
-    ++doublings;
-  }
+  uint64_t cap, doublings;
+  if (!tab_plan_growth(t->cap, need, AS_MAX_CAP, &cap, &doublings))
+    return set_error(c, GS_ENOMEM, "assign state: %llu vertices", (unsigned long long)need);
   GS_TRY(ensure(c, c->ts[11], (t->cap + 2) * 4));
   char* nb;
   AsTable nt;
@@ -542,16 +481,16 @@ gs_status reserve(gs_ctx* c, gs_assign* t, uint64_t need) {
   uint32_t* map = c->ts[11].as<uint32_t>();
   gs_status st = hip_check(c, hipMemsetAsync(t->meta + AS_ERR, 0, 8, c->stream), "hipMemsetAsync");
   if (st == GS_OK) {
-    hipLaunchKernelGGL(k_as_rehash, dim3(as_grid(t->cap + 1)), dim3(256), 0, c->stream, (const AsSlot*)t->tab.slots,
+    hipLaunchKernelGGL(k_as_rehash, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, (const AsSlot*)t->tab.slots,
                        (const uint32_t*)t->tab.lslot, t->cap, nt, map);
     st = hip_check(c, hipGetLastError(), "k_as_rehash");
   }
   if (st == GS_OK) {
-    hipLaunchKernelGGL(k_as_relink, dim3(as_grid(t->cap + 1)), dim3(256), 0, c->stream, (const uint32_t*)t->tab.lslot, t->cap,
+    hipLaunchKernelGGL(k_as_relink, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, (const uint32_t*)t->tab.lslot, t->cap,
                        nt.lslot, (const uint32_t*)map);
     st = hip_check(c, hipGetLastError(), "k_as_relink");
   }
-  if (st == GS_OK) st = read_meta(c, t);
+  if (st == GS_OK) st = tab_read_meta(c, t->meta, AS_META);
   if (st == GS_OK && c->host_small[8 + AS_ERR]) {
     hipMemsetAsync(t->meta + AS_ERR, 0, 8, c->stream);
     st = set_error(c, GS_EDEVICE, "assign state: re-insert failed");
@@ -598,14 +537,14 @@ gs_status run_rounds(gs_ctx* c, gs_assign* t, uint64_t n) {
   t->rounds = t->merging = 0;
   for (int k = 0; k < 4; ++k) t->live_after[k] = 0;
   for (uint32_t round = 0; cnt; ++round) {
-    const dim3 g(as_grid(cnt)), b(256);
+    const dim3 g(tab_grid(cnt)), b(256);
     GS_HIP(hipMemsetAsync(t->meta + AS_PEND, 0, 16, c->stream));   // live edges, finalised edges
     hipLaunchKernelGGL(k_as_find, g, b, 0, c->stream, t->tab, (const uint32_t*)cur, (uint32_t)cnt, round, ra, rb, nxt);
     GS_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_as_decide, g, b, 0, c->stream, t->tab, (const uint32_t*)nxt, (uint32_t)cnt, round,
                        (const uint32_t*)ra, (const uint32_t*)rb, loser);
     GS_HIP(hipGetLastError());
-    GS_TRY(read_meta(c, t));
+    GS_TRY(tab_read_meta(c, t->meta, AS_META));
     const uint64_t live = c->host_small[8 + AS_PEND], fin = c->host_small[8 + AS_FIN];
     if (live == 0) break;
     if (live > cnt || fin > live || fin == 0)
@@ -714,24 +653,24 @@ gs_status gs_assign_edges(gs_ctx* c, gs_assign* t, const gs_edge_batch* b, gs_as
   const AsTable tab = t->tab;
   GS_HIP(hipMemsetAsync(t->meta, 0, AS_META * 8, c->stream));
   GS_TRY(reset_nodes(c, t, true));
-  hipLaunchKernelGGL(k_as_insert, dim3(as_grid_tab(n)), dim3(256), 0, c->stream, tab, src, dst, n, va, vb,
+  hipLaunchKernelGGL(k_as_insert, dim3(tab_grid_tab(n)), dim3(256), 0, c->stream, tab, src, dst, n, va, vb,
                      c->ts[4].as<uint32_t>(), loser);
   GS_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_as_nodes, dim3(as_grid(n)), dim3(256), 0, c->stream, tab, n, (const uint32_t*)va, (const uint32_t*)vb,
+  hipLaunchKernelGGL(k_as_nodes, dim3(tab_grid(n)), dim3(256), 0, c->stream, tab, n, (const uint32_t*)va, (const uint32_t*)vb,
                      c->ts[2].as<uint32_t>(), c->ts[3].as<uint32_t>());
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, AS_META));
   t->occupied += c->host_small[8 + AS_CLAIM];   // the claims stay whatever happens next: outside the state until a batch delivers
   if (c->host_small[8 + AS_ERR]) return set_error(c, GS_EDEVICE, "assign state: the vertex table filled up");
   GS_TRY(run_rounds(c, t, n));
-  hipLaunchKernelGGL(k_as_plabel, dim3(as_grid(n)), dim3(256), 0, c->stream, tab, n, (const uint32_t*)loser);
+  hipLaunchKernelGGL(k_as_plabel, dim3(tab_grid(n)), dim3(256), 0, c->stream, tab, n, (const uint32_t*)loser);
   GS_HIP(hipGetLastError());
-  const dim3 gt(as_grid_tab(t->cap + 1)), bl(256);
+  const dim3 gt(tab_grid_tab(t->cap + 1)), bl(256);
   hipLaunchKernelGGL(k_as_records<true>, gt, bl, 0, c->stream, tab, src, dst, (const uint32_t*)va, (const uint32_t*)vb, AsRec{});
   GS_HIP(hipGetLastError());
   GS_TRY(xscan(c, (const uint64_t*)tab.counts, t->cap + 1, (uint64_t*)tab.pos));
   GS_HIP(hipMemcpyAsync(c->host_small + 8 + AS_META, tab.pos + t->cap + 1, 8, hipMemcpyDeviceToHost, c->stream));
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, AS_META));
   const uint64_t R = c->host_small[8 + AS_META];
   const uint64_t n_new = c->host_small[8 + AS_NEW], n_retired = c->host_small[8 + AS_RETIRED];
   const uint64_t n_loops = c->host_small[8 + AS_LOOPS];
@@ -794,10 +733,10 @@ gs_status gs_assign_edges(gs_ctx* c, gs_assign* t, const gs_edge_batch* b, gs_as
   }
   unsigned long long* ek = c->ct[0].as<unsigned long long>();
   uint32_t* ev = c->ct[2].as<uint32_t>();
-  hipLaunchKernelGGL(k_as_regroup, dim3(as_grid(R)), dim3(256), 0, c->stream, perm, R, (const unsigned long long*)rec.edge, ek, ev);
+  hipLaunchKernelGGL(k_as_regroup, dim3(tab_grid(R)), dim3(256), 0, c->stream, perm, R, (const unsigned long long*)rec.edge, ek, ev);
   GS_HIP(hipGetLastError());
   GS_TRY(sort_buffer(c, (const uint64_t*)ek, ev, R, &s2, 32, 4));
-  hipLaunchKernelGGL(k_as_gather, dim3(as_grid(R)), dim3(256), 0, c->stream, (const uint32_t*)s2.vals, R, rec, ov, ol, oe);
+  hipLaunchKernelGGL(k_as_gather, dim3(tab_grid(R)), dim3(256), 0, c->stream, (const uint32_t*)s2.vals, R, rec, ov, ol, oe);
   GS_HIP(hipGetLastError());
   if (direct) return GS_OK;
   if (out->vertex) GS_TRY(deliver(c, out->vertex, ov, R * 8, out->mem));
@@ -827,9 +766,9 @@ gs_status gs_assign_export(gs_ctx* c, const gs_assign* t, gs_vertex_out* out) {
   unsigned long long* dk = c->ts[7].as<unsigned long long>();
   long long* dl = c->ts[8].as<long long>();
   GS_HIP(hipMemsetAsync(t->meta + AS_DUMP, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_as_dump, dim3(as_grid(t->cap + 1)), dim3(256), 0, c->stream, t->tab, dk, dl, V);
+  hipLaunchKernelGGL(k_as_dump, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, t->tab, dk, dl, V);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, AS_META));
   if (c->host_small[8 + AS_DUMP] != V)
     return set_error(c, GS_EDEVICE, "assign state: %llu vertices in the table, %llu expected",
                      (unsigned long long)c->host_small[8 + AS_DUMP], (unsigned long long)V);
@@ -837,9 +776,9 @@ gs_status gs_assign_export(gs_ctx* c, const gs_assign* t, gs_vertex_out* out) {
   Sorted s;
   GS_TRY(sort_buffer(c, (const uint64_t*)dk, dl, V, &s, 64, 8));
   if (s.wide)
-    hipLaunchKernelGGL(k_as_unkey<uint64_t>, dim3(as_grid(V)), dim3(256), 0, c->stream, (const uint64_t*)s.keys, s.key_xor, V, ok);
+    hipLaunchKernelGGL(k_tab_unkey<uint64_t>, dim3(tab_grid(V)), dim3(256), 0, c->stream, (const uint64_t*)s.keys, s.key_xor, V, ok);
   else
-    hipLaunchKernelGGL(k_as_unkey<uint32_t>, dim3(as_grid(V)), dim3(256), 0, c->stream, (const uint32_t*)s.keys, s.key_xor, V, ok);
+    hipLaunchKernelGGL(k_tab_unkey<uint32_t>, dim3(tab_grid(V)), dim3(256), 0, c->stream, (const uint32_t*)s.keys, s.key_xor, V, ok);
   GS_HIP(hipGetLastError());
   GS_TRY(deliver(c, out->keys, ok, V * 8, out->mem));
   GS_TRY(deliver(c, out->vals, s.vals, V * 8, out->mem));
@@ -871,7 +810,7 @@ gs_status gs_assign_import(gs_ctx* c, gs_assign* t, const gs_partial_batch* rows
   GS_TRY(reserve(c, t, t->occupied + n));
   uint32_t *va = c->ts[0].as<uint32_t>(), *ls = c->ts[1].as<uint32_t>();
   const AsTable tab = t->tab;
-  const dim3 g(as_grid_tab(n)), bl(256);
+  const dim3 g(tab_grid_tab(n)), bl(256);
   GS_HIP(hipMemsetAsync(t->meta, 0, AS_META * 8, c->stream));
   GS_TRY(reset_nodes(c, t, false));
   // the vertices' slots: k_as_insert over (vertex, vertex) rows
@@ -881,7 +820,7 @@ gs_status gs_assign_import(gs_ctx* c, gs_assign* t, const gs_partial_batch* rows
   GS_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_as_import_check, g, bl, 0, c->stream, tab, n, dk, dl, (const uint32_t*)va, ls);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, AS_META));
   t->occupied += c->host_small[8 + AS_CLAIM];
   if (c->host_small[8 + AS_ERR] & 1) return set_error(c, GS_EDEVICE, "assign state: the vertex table filled up");
   if (c->host_small[8 + AS_ERR])
@@ -891,7 +830,7 @@ gs_status gs_assign_import(gs_ctx* c, gs_assign* t, const gs_partial_batch* rows
   t->broken = true;
   hipLaunchKernelGGL(k_as_import_write, g, bl, 0, c->stream, tab, n, dl, (const uint32_t*)va, (const uint32_t*)ls);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, AS_META));
   t->vertices = n;
   t->components = c->host_small[8 + AS_ROOTS];
   t->broken = false;

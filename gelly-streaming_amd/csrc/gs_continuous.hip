@@ -23,56 +23,25 @@
 // The output of one state depends only on the stream, not on how it is cut into batches.
 // Table: slots[cap] of 16 bytes (id, count), so a hit touches one line; cap a power of two, linear probing
 // from a murmur3 finaliser, load <= 1/2 (grown by doubling + re-insert before a batch whose U distinct keys
-// could exceed it).  An empty slot holds CT_EMPTY (the bits of vertex -1); vertex -1 itself lives in a side
+// could exceed it).  An empty slot holds TAB_EMPTY (the bits of vertex -1); vertex -1 itself lives in a side
 // slot (meta[CT_SIDE], present iff its count != 0).
-// Keys only ever change EMPTY -> id, through an agent-scope CAS; counts are touched by their key's one lane.
-#include "gs_ops.hpp"
+// Keys are claimed through gs_table.hpp's tab_claim; counts are touched by their key's one lane.
+#include "gs_table.hpp"
 
 namespace gs {
 
-constexpr unsigned long long CT_EMPTY = ~0ull;
-constexpr unsigned long long CT_SIGN = 1ull << 63;
 enum { CT_DISTINCT = 0, CT_SIDE = 1, CT_ERR = 2, CT_SUM = 3, CT_META = 4 };   // u64 words of gs_cont::meta
 constexpr int CT_EMIT_TILE = 2048;
 
 struct CtTable {
-  unsigned long long* slots;   // [cap][2]: id (or CT_EMPTY), count -- one 16-byte slot, one line per hit
+  unsigned long long* slots;   // [cap][2]: id (or TAB_EMPTY), count -- one 16-byte slot, one line per hit
   unsigned long long mask;     // cap - 1
   unsigned long long* meta;
 };
 
-// the slot of `id` (!= CT_EMPTY), claimed if absent (*fresh); ~0 when the table is full (not reached at
-// load <= 1/2).  A slot read as another id stays that id for good, so only an EMPTY read needs the CAS.
+// the slot of `id` (!= TAB_EMPTY: vertex -1 has the side slot), claimed if absent (*fresh); ~0: the table is full
 __device__ __forceinline__ unsigned long long ct_slot(const CtTable& t, unsigned long long id, bool* fresh) {
-  unsigned long long s = ct_hash(id) & t.mask;
-  for (unsigned long long i = 0; i <= t.mask; ++i, s = (s + 1) & t.mask) {
-    unsigned long long k = __hip_atomic_load(&t.slots[2 * s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == CT_EMPTY) k = atomicCAS(&t.slots[2 * s], CT_EMPTY, id);
-    if (k == CT_EMPTY) {
-      *fresh = true;
-      return s;
-    }
-    if (k == id) {
-      *fresh = false;
-      return s;
-    }
-  }
-  return ~0ull;
-}
-
-// *word += the block's sum of v with one atomic per block (every thread of a 256-thread block calls it, once).
-// One atomic per wave is too many here: nearly every wave of a batch holds some new vertex, and a single
-// word takes ~90 atomics per microsecond (963 000 runs, 15 000 waves: 202 us per call, 72 us this way).
-__device__ __forceinline__ void ct_block_add(unsigned long long* word, unsigned long long v) {
-  __shared__ unsigned long long s_part[4];
-  const unsigned long long inc = wave_inclusive_sum(v);
-  if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long tot = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    if (tot) atomicAdd(word, tot);
-  }
-  __syncthreads();
+  return tab_claim<2>(t.slots, t.mask, id, fresh);
 }
 
 // lane per run u of the batch: base[u] = the vertex's count before the batch, count += the run's length.
@@ -82,13 +51,14 @@ __global__ __launch_bounds__(256) void k_ct_upsert(CtTable t, const int64_t* __r
                                                    const uint64_t* __restrict__ offs, uint32_t U,
                                                    uint64_t* __restrict__ base, const uint32_t* __restrict__ rec,
                                                    uint64_t* __restrict__ flags) {
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long n_fresh = 0;
   for (uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x; u < U; u += (uint64_t)gridDim.x * 256) {
     bool fresh = false;
     const unsigned long long id = (unsigned long long)run_keys[u];
     const uint64_t h = offs[u], len = offs[u + 1] - h;
     uint64_t b = 0;
-    if (id == CT_EMPTY) {
+    if (id == TAB_EMPTY) {
       b = t.meta[CT_SIDE];
       t.meta[CT_SIDE] = b + len;
       fresh = b == 0;
@@ -106,7 +76,7 @@ __global__ __launch_bounds__(256) void k_ct_upsert(CtTable t, const int64_t* __r
     if (FLAG_NEW && fresh) flags[rec[h]] = 1;
     n_fresh += fresh;
   }
-  ct_block_add(&t.meta[CT_DISTINCT], n_fresh);
+  block_add(&t.meta[CT_DISTINCT], n_fresh, s_part);
 }
 
 // largest u in [lo, hi] with offs[u] <= p (offs[lo] <= p given)
@@ -157,10 +127,10 @@ __global__ __launch_bounds__(256) void k_ct_compact(const uint64_t* __restrict__
   }
 }
 
-// every slot free: (CT_EMPTY, 0)
+// every slot free: (TAB_EMPTY, 0)
 __global__ __launch_bounds__(256) void k_ct_clear(ulonglong2* __restrict__ slots, uint64_t cap) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * 256)
-    slots[s] = make_ulonglong2(CT_EMPTY, 0ull);
+    slots[s] = make_ulonglong2(TAB_EMPTY, 0ull);
 }
 
 // growth: every entry of the old table into the new one (keys distinct: claims only)
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(256) void k_ct_rehash(const ulonglong2* __restrict_
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < ocap; s += (uint64_t)gridDim.x * 256) {
     const ulonglong2 o = oslots[s];
     const unsigned long long id = o.x;
-    if (id == CT_EMPTY) continue;
+    if (id == TAB_EMPTY) continue;
     bool fresh;
     const unsigned long long d = ct_slot(t, id, &fresh);
     if (d == ~0ull) atomicOr(&t.meta[CT_ERR], 1ull);
@@ -184,34 +154,20 @@ __global__ __launch_bounds__(256) void k_ct_dump(CtTable t, unsigned long long* 
   if (blockIdx.x == 0 && threadIdx.x == 0 && t.meta[CT_SIDE]) {
     const unsigned long long i = atomicAdd(&t.meta[CT_SUM], 1ull);
     if (i < n) {
-      ok[i] = CT_EMPTY ^ CT_SIGN;
+      ok[i] = TAB_EMPTY ^ TAB_SIGN;
       oc[i] = t.meta[CT_SIDE];
     }
   }
   for (uint64_t s0 = (uint64_t)blockIdx.x * 256; s0 < cap; s0 += stride) {
     const uint64_t s = s0 + threadIdx.x;
-    const unsigned long long id = s < cap ? t.slots[2 * s] : CT_EMPTY;
-    const bool occ = id != CT_EMPTY;
-    const uint64_t m = __ballot(occ);
-    if (!m) continue;
-    const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)m) - 1;
-    unsigned long long first = 0;
-    if (lane == leader) first = atomicAdd(&t.meta[CT_SUM], (unsigned long long)__popcll(m));
-    first = __shfl(first, leader);
-    const unsigned long long i = first + __popcll(m & ((1ull << lane) - 1));
+    const unsigned long long id = s < cap ? t.slots[2 * s] : TAB_EMPTY;
+    const bool occ = id != TAB_EMPTY;
+    const unsigned long long i = wave_compact_base(occ, &t.meta[CT_SUM]);
     if (occ && i < n) {
-      ok[i] = id ^ CT_SIGN;
+      ok[i] = id ^ TAB_SIGN;
       oc[i] = t.slots[2 * s + 1];
     }
   }
-}
-
-// the sorted checkpoint rows back to int64 ids
-template <typename K>
-__global__ __launch_bounds__(256) void k_ct_restore(const K* __restrict__ sk, uint64_t key_xor, uint64_t n,
-                                                    int64_t* __restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-    out[i] = (int64_t)(((uint64_t)sk[i] ^ key_xor) ^ CT_SIGN);
 }
 
 // restore: any count < 1 sets the error word (checked before the table is touched)
@@ -225,13 +181,14 @@ __global__ __launch_bounds__(256) void k_ct_check_counts(const int64_t* __restri
 // restore: lane per row (rows of one vertex add up); meta[CT_SUM] += the counts
 __global__ __launch_bounds__(256) void k_ct_import(CtTable t, const int64_t* __restrict__ keys,
                                                    const int64_t* __restrict__ counts, uint64_t n) {
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long n_fresh = 0, sum = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     bool fresh = false;
     const unsigned long long id = (unsigned long long)keys[i];
     const unsigned long long cnt = (unsigned long long)counts[i];
     sum += cnt;
-    if (id == CT_EMPTY) {
+    if (id == TAB_EMPTY) {
       fresh = atomicAdd(&t.meta[CT_SIDE], cnt) == 0;
     } else {
       const unsigned long long s = ct_slot(t, id, &fresh);
@@ -244,8 +201,8 @@ __global__ __launch_bounds__(256) void k_ct_import(CtTable t, const int64_t* __r
     }
     n_fresh += fresh;
   }
-  ct_block_add(&t.meta[CT_DISTINCT], n_fresh);
-  ct_block_add(&t.meta[CT_SUM], sum);
+  block_add(&t.meta[CT_DISTINCT], n_fresh, s_part);
+  block_add(&t.meta[CT_SUM], sum, s_part);
 }
 
 }  // namespace gs
@@ -262,10 +219,6 @@ struct gs_cont {
 
 namespace {
 
-// the table kernels end in one atomic per block on a shared word: a few blocks per CU, each looping
-unsigned ct_grid_tab(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048)); }
-unsigned ct_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
-
 CtTable table_of(const gs_cont* t) { return CtTable{t->slots, t->cap - 1, t->meta}; }
 
 // a table of cap free slots (cleared in the ctx stream's order)
@@ -277,7 +230,7 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, unsigned long long** slots) {
     return set_error(c, GS_ENOMEM, "continuous state: a vertex table of %llu slots does not fit",
                      (unsigned long long)cap);
   }
-  hipLaunchKernelGGL(k_ct_clear, dim3(ct_grid(cap)), dim3(256), 0, c->stream, (ulonglong2*)*slots, cap);
+  hipLaunchKernelGGL(k_ct_clear, dim3(tab_grid(cap)), dim3(256), 0, c->stream, (ulonglong2*)*slots, cap);
   const gs_status st = hip_check(c, hipGetLastError(), "k_ct_clear");
   if (st != GS_OK) {
     hipFree(*slots);
@@ -286,31 +239,23 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, unsigned long long** slots) {
   return st;
 }
 
-// the state's device words -> host_small[8 .. 8 + CT_META), and a wait for the stream
-gs_status read_meta(gs_ctx* c, const gs_cont* t) {
-  GS_HIP(hipMemcpyAsync(c->host_small + 8, t->meta, CT_META * 8, hipMemcpyDeviceToHost, c->stream));
-  return host_wait(c);
-}
-
 // room for `need` distinct vertices at load <= 1/2: grow by doubling (allocate, re-insert, swap).  On any
 // failure the old table stays as it was.
 gs_status reserve(gs_ctx* c, gs_cont* t, uint64_t need) {
   if (need <= t->cap / 2) return GS_OK;
-  uint64_t cap = t->cap, doublings = 0;
-  while (need > cap / 2) {
-    if (cap > (1ull << 40)) return set_error(c, GS_ENOMEM, "continuous state: %llu vertices", (unsigned long long)need);
-    cap *= 2;
-    ++doublings;
-  }
+  uint64_t cap, doublings;
+  // a table of 2^40 slots may still double: alloc_table refuses the 2^41 it plans
+  if (!tab_plan_growth(t->cap, need, 1ull << 41, &cap, &doublings))
+    return set_error(c, GS_ENOMEM, "continuous state: %llu vertices", (unsigned long long)need);
   unsigned long long* ns;
   GS_TRY(alloc_table(c, cap, &ns));
   gs_status st = GS_OK;
   if (t->distinct) {
-    hipLaunchKernelGGL(k_ct_rehash, dim3(ct_grid(t->cap)), dim3(256), 0, c->stream, (const ulonglong2*)t->slots, t->cap,
+    hipLaunchKernelGGL(k_ct_rehash, dim3(tab_grid(t->cap)), dim3(256), 0, c->stream, (const ulonglong2*)t->slots, t->cap,
                        CtTable{ns, cap - 1, t->meta});
     st = hip_check(c, hipGetLastError(), "k_ct_rehash");
   }
-  if (st == GS_OK) st = read_meta(c, t);
+  if (st == GS_OK) st = tab_read_meta(c, t->meta, CT_META);
   if (st == GS_OK && c->host_small[8 + CT_ERR]) st = set_error(c, GS_EDEVICE, "continuous state: re-insert failed");
   if (st != GS_OK) {
     hipFree(ns);
@@ -382,28 +327,28 @@ gs_status cont_batch(gs_ctx* c, gs_cont* t, const gs_edge_batch* b, int32_t dir,
     uint64_t* flags = c->ct[3].as<uint64_t>();
     uint64_t* pos = c->ct[4].as<uint64_t>();
     GS_HIP(hipMemsetAsync(flags, 0, R * 8, c->stream));
-    hipLaunchKernelGGL(k_ct_upsert<true>, dim3(ct_grid_tab(U)), dim3(256), 0, c->stream, table_of(t), rk, offs, (uint32_t)U,
+    hipLaunchKernelGGL(k_ct_upsert<true>, dim3(tab_grid_tab(U)), dim3(256), 0, c->stream, table_of(t), rk, offs, (uint32_t)U,
                        base, rec, flags);
     GS_HIP(hipGetLastError());
     GS_TRY(xscan(c, flags, R, pos));
-    hipLaunchKernelGGL(k_ct_compact, dim3(ct_grid(R)), dim3(256), 0, c->stream, flags, pos, (uint32_t)R, src, dst, before,
+    hipLaunchKernelGGL(k_ct_compact, dim3(tab_grid(R)), dim3(256), 0, c->stream, flags, pos, (uint32_t)R, src, dst, before,
                        ov, ox);
     GS_HIP(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(k_ct_upsert<false>, dim3(ct_grid_tab(U)), dim3(256), 0, c->stream, table_of(t), rk, offs, (uint32_t)U,
+    hipLaunchKernelGGL(k_ct_upsert<false>, dim3(tab_grid_tab(U)), dim3(256), 0, c->stream, table_of(t), rk, offs, (uint32_t)U,
                        base, rec, (uint64_t*)nullptr);
     GS_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ct_emit, dim3((unsigned)((R + CT_EMIT_TILE - 1) / CT_EMIT_TILE)), dim3(256), 0, c->stream, offs,
                        base, (uint32_t)U, rec, (uint32_t)R, ox);
     GS_HIP(hipGetLastError());
     if (dir == GS_DIR_ALL) {
-      hipLaunchKernelGGL(k_ct_expand_all, dim3(ct_grid(R)), dim3(256), 0, c->stream, src, dst, b->n, ov);
+      hipLaunchKernelGGL(k_ct_expand_all, dim3(tab_grid(R)), dim3(256), 0, c->stream, src, dst, b->n, ov);
       GS_HIP(hipGetLastError());
     } else {
       GS_HIP(hipMemcpyAsync(ov, dir == GS_DIR_OUT ? src : dst, R * 8, hipMemcpyDeviceToDevice, c->stream));
     }
   }
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, CT_META));
   if (c->host_small[8 + CT_ERR]) return set_error(c, GS_EDEVICE, "continuous state: the vertex table filled up");
   t->distinct = c->host_small[8 + CT_DISTINCT];
   t->records += R;
@@ -500,9 +445,9 @@ gs_status gs_cont_export(gs_ctx* c, const gs_cont* t, gs_vertex_out* out) {
   unsigned long long* dk = c->ct[0].as<unsigned long long>();
   unsigned long long* dc = c->ct[1].as<unsigned long long>();
   GS_HIP(hipMemsetAsync(t->meta + CT_SUM, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_ct_dump, dim3(ct_grid(t->cap)), dim3(256), 0, c->stream, table_of(t), dk, dc, D);
+  hipLaunchKernelGGL(k_ct_dump, dim3(tab_grid(t->cap)), dim3(256), 0, c->stream, table_of(t), dk, dc, D);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, CT_META));
   if (c->host_small[8 + CT_SUM] != D)
     return set_error(c, GS_EDEVICE, "continuous state: %llu entries in the table, %llu expected",
                      (unsigned long long)c->host_small[8 + CT_SUM], (unsigned long long)D);
@@ -510,10 +455,10 @@ gs_status gs_cont_export(gs_ctx* c, const gs_cont* t, gs_vertex_out* out) {
   Sorted s;
   GS_TRY(sort_buffer(c, (const uint64_t*)dk, dc, D, &s, 64, 8));
   if (s.wide)
-    hipLaunchKernelGGL(k_ct_restore<uint64_t>, dim3(ct_grid(D)), dim3(256), 0, c->stream, (const uint64_t*)s.keys,
+    hipLaunchKernelGGL(k_tab_unkey<uint64_t>, dim3(tab_grid(D)), dim3(256), 0, c->stream, (const uint64_t*)s.keys,
                        s.key_xor, D, ok);
   else
-    hipLaunchKernelGGL(k_ct_restore<uint32_t>, dim3(ct_grid(D)), dim3(256), 0, c->stream, (const uint32_t*)s.keys,
+    hipLaunchKernelGGL(k_tab_unkey<uint32_t>, dim3(tab_grid(D)), dim3(256), 0, c->stream, (const uint32_t*)s.keys,
                        s.key_xor, D, ok);
   GS_HIP(hipGetLastError());
   GS_TRY(deliver(c, out->keys, ok, D * 8, out->mem));
@@ -541,18 +486,18 @@ gs_status gs_cont_import(gs_ctx* c, gs_cont* t, const gs_partial_batch* rows) {
     dc = c->ct[1].as<int64_t>();
   }
   GS_HIP(hipMemsetAsync(t->meta + CT_ERR, 0, 16, c->stream));   // error word, count sum
-  hipLaunchKernelGGL(k_ct_check_counts, dim3(ct_grid(n)), dim3(256), 0, c->stream, dc, n, t->meta + CT_ERR);
+  hipLaunchKernelGGL(k_ct_check_counts, dim3(tab_grid(n)), dim3(256), 0, c->stream, dc, n, t->meta + CT_ERR);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, CT_META));
   if (c->host_small[8 + CT_ERR]) {
     GS_HIP(hipMemsetAsync(t->meta + CT_ERR, 0, 8, c->stream));
     return set_error(c, GS_EINVAL, "gs_cont_import: every count must be at least 1");
   }
   GS_TRY(reserve(c, t, n));
   // ---- the table changes from here on ----
-  hipLaunchKernelGGL(k_ct_import, dim3(ct_grid_tab(n)), dim3(256), 0, c->stream, table_of(t), dk, dc, n);
+  hipLaunchKernelGGL(k_ct_import, dim3(tab_grid_tab(n)), dim3(256), 0, c->stream, table_of(t), dk, dc, n);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, CT_META));
   if (c->host_small[8 + CT_ERR]) return set_error(c, GS_EDEVICE, "continuous state: the vertex table filled up");
   t->distinct = c->host_small[8 + CT_DISTINCT];
   t->records = c->host_small[8 + CT_SUM];

@@ -28,11 +28,10 @@
 //                  its slot -> (tag,0,before + k).  Only the winner writes its slot.
 // The slot words are read and written with agent-scope atomics inside k_ds_claim (lanes of other CUs change
 // them meanwhile); everything else a kernel reads was written by an earlier kernel or copy of the stream.
-#include "gs_ops.hpp"
+#include "gs_table.hpp"
 
 namespace gs {
 
-constexpr unsigned long long DS_EMPTY = ~0ull;
 constexpr unsigned long long DS_NONE = ~0ull;            // held[i]: edge i holds no slot
 constexpr unsigned long long DS_BATCH = 1ull << 40;
 constexpr unsigned long long DS_INDEX = DS_BATCH - 1;
@@ -65,9 +64,9 @@ __global__ __launch_bounds__(256) void k_ds_claim(DsTable t, const int64_t* __re
     bool done = false;
     for (unsigned long long probes = 0; probes <= t.mask && !done; ++probes, slot = (slot + 1) & t.mask) {
       unsigned long long w = __hip_atomic_load(&t.slots[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (w == DS_EMPTY) {
-        w = atomicCAS(&t.slots[slot], DS_EMPTY, mine);
-        if (w == DS_EMPTY) {
+      if (w == TAB_EMPTY) {
+        w = atomicCAS(&t.slots[slot], TAB_EMPTY, mine);
+        if (w == TAB_EMPTY) {
           got = slot;
           done = true;
           break;
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(256) void k_ds_compact(unsigned long long* __restri
 }
 
 __global__ __launch_bounds__(256) void k_ds_clear(unsigned long long* __restrict__ slots, uint64_t cap) {
-  for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * 256) slots[s] = DS_EMPTY;
+  for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * 256) slots[s] = TAB_EMPTY;
 }
 
 // growth: a streaming read of the log into a cleared table (the log's keys are distinct: claims only)
@@ -149,8 +148,8 @@ __global__ __launch_bounds__(256) void k_ds_rebuild(DsTable t, uint64_t D) {
     bool done = false;
     for (unsigned long long probes = 0; probes <= t.mask; ++probes, slot = (slot + 1) & t.mask) {
       unsigned long long w = __hip_atomic_load(&t.slots[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (w == DS_EMPTY) w = atomicCAS(&t.slots[slot], DS_EMPTY, mine);
-      if (w == DS_EMPTY) {
+      if (w == TAB_EMPTY) w = atomicCAS(&t.slots[slot], TAB_EMPTY, mine);
+      if (w == TAB_EMPTY) {
         done = true;
         break;
       }
@@ -180,8 +179,6 @@ namespace {
 constexpr uint64_t DS_MAX_CAP = 1ull << 40;   // 2^39 log entries: below the 40 index bits of a slot word
 constexpr uint64_t DS_CHUNK = 1ull << 31;     // gs_distinct_import: rows per pass
 
-unsigned ds_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
-
 DsTable table_of(const gs_distinct* t) { return DsTable{t->slots, t->cap - 1, t->log_src, t->log_dst, t->meta}; }
 
 void free_tables(unsigned long long* slots, int64_t* ls, int64_t* ld) {
@@ -202,7 +199,7 @@ gs_status alloc_tables(gs_ctx* c, uint64_t cap, unsigned long long** slots, int6
     *ls = *ld = nullptr;
     return set_error(c, GS_ENOMEM, "distinct state: an edge table of %llu slots does not fit", (unsigned long long)cap);
   }
-  hipLaunchKernelGGL(k_ds_clear, dim3(ds_grid(cap)), dim3(256), 0, c->stream, *slots, cap);
+  hipLaunchKernelGGL(k_ds_clear, dim3(tab_grid(cap)), dim3(256), 0, c->stream, *slots, cap);
   const gs_status st = hip_check(c, hipGetLastError(), "k_ds_clear");
   if (st != GS_OK) {
     free_tables(*slots, *ls, *ld);
@@ -212,22 +209,13 @@ gs_status alloc_tables(gs_ctx* c, uint64_t cap, unsigned long long** slots, int6
   return st;
 }
 
-// the state's device words -> host_small[8 .. 8 + DS_META), and a wait for the stream
-gs_status read_meta(gs_ctx* c, const gs_distinct* t) {
-  GS_HIP(hipMemcpyAsync(c->host_small + 8, t->meta, DS_META * 8, hipMemcpyDeviceToHost, c->stream));
-  return host_wait(c);
-}
-
 // room for `need` distinct edges at load <= 1/2, table and log: grow by doubling (allocate, copy the log,
 // rebuild the slots from it, swap).  On any failure the old state stays as it was.
 gs_status reserve(gs_ctx* c, gs_distinct* t, uint64_t need) {
   if (need <= t->cap / 2) return GS_OK;
-  uint64_t cap = t->cap, doublings = 0;
-  while (need > cap / 2) {
-    if (cap >= DS_MAX_CAP) return set_error(c, GS_ENOMEM, "distinct state: %llu edges", (unsigned long long)need);
-    cap *= 2;
-    ++doublings;
-  }
+  uint64_t cap, doublings;
+  if (!tab_plan_growth(t->cap, need, DS_MAX_CAP, &cap, &doublings))
+    return set_error(c, GS_ENOMEM, "distinct state: %llu edges", (unsigned long long)need);
   unsigned long long* ns;
   int64_t *nls, *nld;
   GS_TRY(alloc_tables(c, cap, &ns, &nls, &nld));
@@ -239,13 +227,13 @@ gs_status reserve(gs_ctx* c, gs_distinct* t, uint64_t need) {
     if (st == GS_OK) {
       const DsTable nt{ns, cap - 1, nls, nld, t->meta};
       if (t->mode == GS_DISTINCT_KEYED)
-        hipLaunchKernelGGL(k_ds_rebuild<true>, dim3(ds_grid(D)), dim3(256), 0, c->stream, nt, D);
+        hipLaunchKernelGGL(k_ds_rebuild<true>, dim3(tab_grid(D)), dim3(256), 0, c->stream, nt, D);
       else
-        hipLaunchKernelGGL(k_ds_rebuild<false>, dim3(ds_grid(D)), dim3(256), 0, c->stream, nt, D);
+        hipLaunchKernelGGL(k_ds_rebuild<false>, dim3(tab_grid(D)), dim3(256), 0, c->stream, nt, D);
       st = hip_check(c, hipGetLastError(), "k_ds_rebuild");
     }
   }
-  if (st == GS_OK) st = read_meta(c, t);
+  if (st == GS_OK) st = tab_read_meta(c, t->meta, DS_META);
   if (st == GS_OK && c->host_small[8 + DS_ERR]) st = set_error(c, GS_EDEVICE, "distinct state: rebuild failed");
   if (st != GS_OK) {
     free_tables(ns, nls, nld);
@@ -272,7 +260,7 @@ gs_status check_state(gs_ctx* c, const gs_distinct* t) {
 template <bool KEYED>
 void launch_compact(gs_ctx* c, gs_distinct* t, const int64_t* src, const int64_t* dst, const void* val, int vb, uint64_t n,
                     const unsigned long long* held, const uint64_t* keep, const uint64_t* pos, DsOut o) {
-  const dim3 g(ds_grid(n)), b(256);
+  const dim3 g(tab_grid(n)), b(256);
   if (vb == 4)
     hipLaunchKernelGGL((k_ds_compact<KEYED, 4>), g, b, 0, c->stream, t->slots, t->log_src, t->log_dst, src, dst, val, n, held,
                        keep, pos, t->distinct, o);
@@ -299,7 +287,7 @@ gs_status run_batch(gs_ctx* c, gs_distinct* t, const int64_t* src, const int64_t
   uint64_t* keep = c->ct[3].as<uint64_t>();
   uint64_t* pos = c->ct[4].as<uint64_t>();
   const bool keyed = t->mode == GS_DISTINCT_KEYED;
-  const dim3 g(ds_grid(n)), b(256);
+  const dim3 g(tab_grid(n)), b(256);
   // ---- the table changes from here on ----
   t->broken = true;
   if (keyed) hipLaunchKernelGGL(k_ds_claim<true>, g, b, 0, c->stream, table_of(t), src, dst, n, held);
@@ -312,7 +300,7 @@ gs_status run_batch(gs_ctx* c, gs_distinct* t, const int64_t* src, const int64_t
   else launch_compact<false>(c, t, src, dst, val, o.val ? vb : 0, n, held, keep, pos, o);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(c->host_small + 8 + DS_META, pos + n, 8, hipMemcpyDeviceToHost, c->stream));
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, DS_META));
   if (c->host_small[8 + DS_ERR]) return set_error(c, GS_EDEVICE, "distinct state: the edge table filled up");
   *kept = c->host_small[8 + DS_META];
   if (*kept > n) return set_error(c, GS_EDEVICE, "distinct state: %llu kept of %llu edges", (unsigned long long)*kept,

@@ -39,12 +39,10 @@
 // nothing ends the call with GS_EDEVICE.  No device-side waits, no grid-wide barriers.
 // Every touched vertex is a batch endpoint or the batch-start partner of one; k_mt_insert saves those slots'
 // (weight, link), and a call that cannot deliver (GS_ECAPACITY, an allocation) puts them back (k_mt_restore).
-#include "gs_ops.hpp"
+#include "gs_table.hpp"
 
 namespace gs {
 
-constexpr unsigned long long MT_EMPTY = ~0ull;
-constexpr unsigned long long MT_SIGN = 1ull << 63;
 constexpr unsigned long long MT_MATCHED = 1ull << 32, MT_SRC = 1ull << 33;
 constexpr uint32_t MT_NONE = 0xFFFFFFFFu;   // footprint entry: no vertex
 constexpr int MT_TAIL = 1024;               // pending edges one workgroup finishes by itself
@@ -64,37 +62,12 @@ struct MtTable {
   unsigned long long* meta;
 };
 
-// the slot of `id`, claimed if absent (*fresh); MT_NONE when the table is full (not reached at load <= 1/2)
+// the slot of `id`, claimed if absent (*fresh); vertex -1: the side slot, never fresh; MT_NONE (what tab_claim's
+// ~0 narrows to: slots stay below 2^31) when the table is full
 __device__ __forceinline__ uint32_t mt_slot(const MtTable& t, unsigned long long id, bool* fresh) {
   *fresh = false;
-  if (id == MT_EMPTY) return (uint32_t)(t.mask + 1);
-  unsigned long long s = ct_hash(id) & t.mask;
-  for (unsigned long long i = 0; i <= t.mask; ++i, s = (s + 1) & t.mask) {
-    unsigned long long k = __hip_atomic_load(&t.slots[s].id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == MT_EMPTY) {
-      k = atomicCAS(&t.slots[s].id, MT_EMPTY, id);
-      if (k == MT_EMPTY) {
-        *fresh = true;
-        return (uint32_t)s;
-      }
-    }
-    if (k == id) return (uint32_t)s;
-  }
-  return MT_NONE;
-}
-
-// *word += the block's sum of v (every thread of the block calls it, once per word and kernel)
-__device__ __forceinline__ void mt_block_add(unsigned long long* word, unsigned long long v, unsigned long long* s_part) {
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-  const int waves = (blockDim.x + 63) >> 6;
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long tot = 0;
-    for (int i = 0; i < waves; ++i) tot += s_part[i];
-    if (tot) atomicAdd(word, tot);
-  }
-  __syncthreads();
+  if (id == TAB_EMPTY) return (uint32_t)(t.mask + 1);
+  return (uint32_t)tab_claim<sizeof(MtSlot) / 8>(&t.slots->id, t.mask, id, fresh);
 }
 
 __device__ __forceinline__ unsigned long long mt_word(uint32_t epoch, uint32_t i) {
@@ -194,7 +167,7 @@ __device__ __forceinline__ void mt_save(const MtTable& t, uint32_t s) {
 __global__ __launch_bounds__(256) void k_mt_insert(MtTable t, const int64_t* __restrict__ bs, const int64_t* __restrict__ bd,
                                                    uint64_t n, uint32_t* __restrict__ su, uint32_t* __restrict__ sv,
                                                    uint32_t* __restrict__ pend) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long n_fresh = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     bool fa, fb;
@@ -212,7 +185,7 @@ __global__ __launch_bounds__(256) void k_mt_insert(MtTable t, const int64_t* __r
     }
     if (pend) pend[i] = (uint32_t)i;
   }
-  mt_block_add(&t.meta[MT_FRESH], n_fresh, s_part);
+  block_add(&t.meta[MT_FRESH], n_fresh, s_part);
 }
 
 // a batch that cannot deliver: every slot it may have touched back to its saved (weight, link)
@@ -288,13 +261,8 @@ __global__ __launch_bounds__(256) void k_mt_final(MtTable t, const uint32_t* __r
         else stay = true;
       }
     }
-    const unsigned long long m = __ballot(stay);
-    if (!m) continue;
-    const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)m) - 1;
-    unsigned long long first = 0;
-    if (lane == leader) first = atomicAdd(&t.meta[MT_PEND], (unsigned long long)__popcll(m));
-    first = __shfl(first, leader);
-    if (stay) next[first + __popcll(m & ((1ull << lane) - 1))] = i;
+    const unsigned long long k = wave_compact_base(stay, &t.meta[MT_PEND]);
+    if (stay) next[k] = i;
   }
 }
 
@@ -371,7 +339,7 @@ __global__ __launch_bounds__(256) void k_mt_emit(const int64_t* __restrict__ bs,
                                                  const int64_t* __restrict__ bw, uint64_t n, const uint64_t* __restrict__ nev,
                                                  const uint64_t* __restrict__ pos, const long long* __restrict__ rem, MtOut o,
                                                  unsigned long long* __restrict__ meta) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long dcnt = 0, dw = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     const uint64_t e = nev[i];
@@ -394,14 +362,14 @@ __global__ __launch_bounds__(256) void k_mt_emit(const int64_t* __restrict__ bs,
     dw += (unsigned long long)bw[i];
     dcnt += 2ull - e;
   }
-  mt_block_add(&meta[MT_DCNT], dcnt, s_part);
-  mt_block_add(&meta[MT_DW], dw, s_part);
+  block_add(&meta[MT_DCNT], dcnt, s_part);
+  block_add(&meta[MT_DW], dw, s_part);
 }
 
 // every slot free and unmatched; the side slot's id is vertex -1 from the start
 __global__ __launch_bounds__(256) void k_mt_clear(MtSlot* __restrict__ slots, uint64_t cap) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= cap; s += (uint64_t)gridDim.x * 256)
-    slots[s] = MtSlot{MT_EMPTY, 0ull, 0ull, 0ull};
+    slots[s] = MtSlot{TAB_EMPTY, 0ull, 0ull, 0ull};
 }
 
 // the epoch counter is about to wrap: every reservation word back to "no round"
@@ -414,7 +382,7 @@ __global__ __launch_bounds__(256) void k_mt_rehash(const MtSlot* __restrict__ os
                                                    uint32_t* __restrict__ map) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= ocap; s += (uint64_t)gridDim.x * 256) {
     const unsigned long long id = os[s].id;
-    if (s < ocap && id == MT_EMPTY) continue;
+    if (s < ocap && id == TAB_EMPTY) continue;
     bool fresh;
     const uint32_t d = mt_slot(t, id, &fresh);
     map[s] = d;
@@ -427,7 +395,7 @@ __global__ __launch_bounds__(256) void k_mt_relink(const MtSlot* __restrict__ os
                                                    const uint32_t* __restrict__ map) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= ocap; s += (uint64_t)gridDim.x * 256) {
     const unsigned long long l = os[s].link;
-    if (!(l & MT_MATCHED) || (s < ocap && os[s].id == MT_EMPTY)) continue;
+    if (!(l & MT_MATCHED) || (s < ocap && os[s].id == TAB_EMPTY)) continue;
     const uint32_t d = map[s], p = map[(uint32_t)l];
     if (d != MT_NONE && p != MT_NONE) ns[d].link = (l & ~0xFFFFFFFFull) | p;
   }
@@ -445,7 +413,7 @@ __global__ __launch_bounds__(256) void k_mt_dump(MtTable t, unsigned long long* 
     const unsigned long long k = atomicAdd(&t.meta[MT_PEND], 1ull);
     if (k >= M) continue;
     const unsigned long long id = t.slots[s].id;
-    keys[k] = id ^ MT_SIGN;
+    keys[k] = id ^ TAB_SIGN;
     rows[k] = (uint32_t)k;
     es[k] = (int64_t)id;
     ed[k] = (int64_t)t.slots[(uint32_t)l].id;
@@ -483,7 +451,7 @@ __global__ __launch_bounds__(256) void k_mt_import_check(MtTable t, uint64_t n, 
 }
 __global__ __launch_bounds__(256) void k_mt_import_write(MtTable t, uint64_t n, const uint32_t* __restrict__ su,
                                                          const uint32_t* __restrict__ sv, const int64_t* __restrict__ bw) {
-  __shared__ unsigned long long s_part[4];
+  __shared__ unsigned long long s_part[TAB_PART];
   unsigned long long dw = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     const uint32_t a = su[i], b = sv[i];
@@ -496,7 +464,7 @@ __global__ __launch_bounds__(256) void k_mt_import_write(MtTable t, uint64_t n, 
     }
     dw += w;
   }
-  mt_block_add(&t.meta[MT_DW], dw, s_part);
+  block_add(&t.meta[MT_DW], dw, s_part);
 }
 
 }  // namespace gs
@@ -521,9 +489,6 @@ namespace {
 
 constexpr uint64_t MT_MAX_CAP = 1ull << 31;   // slot numbers are 32-bit, cap itself is vertex -1's
 
-unsigned mt_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
-unsigned mt_grid_tab(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048)); }
-
 MtTable table_of(const gs_match* t) { return MtTable{t->slots, t->saved, t->cap - 1, t->meta}; }
 
 gs_status alloc_table(gs_ctx* c, uint64_t cap, MtSlot** slots, ulonglong2** saved) {
@@ -537,7 +502,7 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, MtSlot** slots, ulonglong2** save
     *saved = nullptr;
     return set_error(c, GS_ENOMEM, "matching state: a vertex table of %llu slots does not fit", (unsigned long long)cap);
   }
-  hipLaunchKernelGGL(k_mt_clear, dim3(mt_grid(cap + 1)), dim3(256), 0, c->stream, *slots, cap);
+  hipLaunchKernelGGL(k_mt_clear, dim3(tab_grid(cap + 1)), dim3(256), 0, c->stream, *slots, cap);
   const gs_status st = hip_check(c, hipGetLastError(), "k_mt_clear");
   if (st != GS_OK) {
     hipFree(*slots);
@@ -548,22 +513,13 @@ gs_status alloc_table(gs_ctx* c, uint64_t cap, MtSlot** slots, ulonglong2** save
   return st;
 }
 
-// the state's device words -> host_small[8 .. 8 + MT_META), and a wait for the stream
-gs_status read_meta(gs_ctx* c, const gs_match* t) {
-  GS_HIP(hipMemcpyAsync(c->host_small + 8, t->meta, MT_META * 8, hipMemcpyDeviceToHost, c->stream));
-  return host_wait(c);
-}
-
 // room for `need` vertices at load <= 1/2: grow by doubling (allocate, re-insert, swap).  On any failure the
 // old table stays as it was.
 gs_status reserve(gs_ctx* c, gs_match* t, uint64_t need) {
   if (need <= t->cap / 2) return GS_OK;
-  uint64_t cap = t->cap, doublings = 0;
-  while (need > cap / 2) {
-    if (cap >= MT_MAX_CAP) return set_error(c, GS_ENOMEM, "matching state: %llu vertices", (unsigned long long)need);
-    cap *= 2;
-    ++doublings;
-  }
+  uint64_t cap, doublings;
+  if (!tab_plan_growth(t->cap, need, MT_MAX_CAP, &cap, &doublings))
+    return set_error(c, GS_ENOMEM, "matching state: %llu vertices", (unsigned long long)need);
   GS_TRY(ensure(c, c->ts[9], (t->cap + 1) * 4));
   MtSlot* ns;
   ulonglong2* nsv;
@@ -576,15 +532,15 @@ gs_status reserve(gs_ctx* c, gs_match* t, uint64_t need) {
     hipFree(nsv);
     return pre;
   }
-  hipLaunchKernelGGL(k_mt_rehash, dim3(mt_grid(t->cap + 1)), dim3(256), 0, c->stream, (const MtSlot*)t->slots, t->cap,
+  hipLaunchKernelGGL(k_mt_rehash, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, (const MtSlot*)t->slots, t->cap,
                      MtTable{ns, nsv, cap - 1, t->meta}, map);
   gs_status st = hip_check(c, hipGetLastError(), "k_mt_rehash");
   if (st == GS_OK) {
-    hipLaunchKernelGGL(k_mt_relink, dim3(mt_grid(t->cap + 1)), dim3(256), 0, c->stream, (const MtSlot*)t->slots, t->cap, ns,
+    hipLaunchKernelGGL(k_mt_relink, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, (const MtSlot*)t->slots, t->cap, ns,
                        (const uint32_t*)map);
     st = hip_check(c, hipGetLastError(), "k_mt_relink");
   }
-  if (st == GS_OK) st = read_meta(c, t);
+  if (st == GS_OK) st = tab_read_meta(c, t->meta, MT_META);
   if (st == GS_OK && c->host_small[8 + MT_ERR]) {
     hipMemsetAsync(t->meta + MT_ERR, 0, 8, c->stream);
     st = set_error(c, GS_EDEVICE, "matching state: re-insert failed");
@@ -615,7 +571,7 @@ gs_status check_state(gs_ctx* c, const gs_match* t) {
 // room for the round tags of a batch of n edges; the words start over before the 32-bit tag would wrap
 gs_status reserve_epochs(gs_ctx* c, gs_match* t, uint64_t n) {
   if ((uint64_t)t->epoch + n + 2 < (1ull << 32)) return GS_OK;
-  hipLaunchKernelGGL(k_mt_clear_resv, dim3(mt_grid(t->cap + 1)), dim3(256), 0, c->stream, t->slots, t->cap);
+  hipLaunchKernelGGL(k_mt_clear_resv, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, t->slots, t->cap);
   GS_HIP(hipGetLastError());
   t->epoch = 0;
   return GS_OK;
@@ -632,10 +588,10 @@ gs_status ensure_slots(gs_ctx* c, uint64_t n) {
 gs_status insert_batch(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* dst, uint64_t n, uint32_t* pend) {
   GS_HIP(hipMemsetAsync(t->meta, 0, MT_META * 8, c->stream));
   t->broken = true;
-  hipLaunchKernelGGL(k_mt_insert, dim3(mt_grid_tab(n)), dim3(256), 0, c->stream, table_of(t), src, dst, n,
+  hipLaunchKernelGGL(k_mt_insert, dim3(tab_grid_tab(n)), dim3(256), 0, c->stream, table_of(t), src, dst, n,
                      c->ts[0].as<uint32_t>(), c->ts[1].as<uint32_t>(), pend);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, MT_META));
   if (c->host_small[8 + MT_ERR]) return set_error(c, GS_EDEVICE, "matching state: the vertex table filled up");
   t->vertices += c->host_small[8 + MT_FRESH];
   t->broken = false;
@@ -659,7 +615,7 @@ gs_status run_rounds(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* 
       hipLaunchKernelGGL(k_mt_tail, dim3(1), dim3(MT_TAIL), 0, c->stream, tab, (const uint32_t*)cur, (uint32_t)cnt, su, sv, src,
                          dst, val, t->epoch + 1, nev, rem, (uint32_t)std::min<uint64_t>(t->rounds, 1u << 30));
       GS_HIP(hipGetLastError());
-      GS_TRY(read_meta(c, t));
+      GS_TRY(tab_read_meta(c, t->meta, MT_META));
       const uint64_t* m = c->host_small + 8;
       t->epoch += (uint32_t)m[MT_TROUNDS];
       for (int k = 0; k < 4; ++k)
@@ -671,7 +627,7 @@ gs_status run_rounds(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* 
       break;
     }
     const uint32_t epoch = ++t->epoch;
-    const dim3 g(mt_grid(cnt)), b(256);
+    const dim3 g(tab_grid(cnt)), b(256);
     GS_HIP(hipMemsetAsync(t->meta + MT_PEND, 0, (1 + MT_BLOCK_GROUP) * 8, c->stream));
     hipLaunchKernelGGL(k_mt_eval, g, b, 0, c->stream, tab, (const uint32_t*)cur, (uint32_t)cnt, su, sv, val, epoch, fps, st);
     GS_HIP(hipGetLastError());
@@ -682,7 +638,7 @@ gs_status run_rounds(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* 
         hipLaunchKernelGGL(k_mt_block, g, b, 0, c->stream, tab, (const uint32_t*)cur, (uint32_t)cnt, epoch, (const uint4*)fps, st,
                            t->meta + MT_CHG + k);
       GS_HIP(hipGetLastError());
-      GS_TRY(read_meta(c, t));
+      GS_TRY(tab_read_meta(c, t->meta, MT_META));
       int done = 0;
       while (done < MT_BLOCK_GROUP && c->host_small[8 + MT_CHG + done]) ++done;
       t->block_iters += std::min(done + 1, MT_BLOCK_GROUP);
@@ -692,7 +648,7 @@ gs_status run_rounds(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* 
     hipLaunchKernelGGL(k_mt_final, g, b, 0, c->stream, tab, (const uint32_t*)cur, (uint32_t)cnt, su, sv, src, dst, val, epoch,
                        (const uint4*)fps, (const uint8_t*)st, nev, rem, nxt);
     GS_HIP(hipGetLastError());
-    GS_TRY(read_meta(c, t));
+    GS_TRY(tab_read_meta(c, t->meta, MT_META));
     const uint64_t left = c->host_small[8 + MT_PEND];
     ++t->rounds;
     for (int k = 0; k < 4; ++k)
@@ -706,7 +662,7 @@ gs_status run_rounds(gs_ctx* c, gs_match* t, const int64_t* src, const int64_t* 
 }
 
 gs_status restore_batch(gs_ctx* c, gs_match* t, uint64_t n) {
-  hipLaunchKernelGGL(k_mt_restore, dim3(mt_grid(n)), dim3(256), 0, c->stream, table_of(t), n, (const uint32_t*)c->ts[0].p,
+  hipLaunchKernelGGL(k_mt_restore, dim3(tab_grid(n)), dim3(256), 0, c->stream, table_of(t), n, (const uint32_t*)c->ts[0].p,
                      (const uint32_t*)c->ts[1].p);
   GS_HIP(hipGetLastError());
   GS_TRY(host_wait(c));
@@ -846,10 +802,10 @@ gs_status gs_match_edges(gs_ctx* c, gs_match* t, const gs_edge_batch* b, gs_matc
       return set_error(c, st, "%s", why.c_str());
     }
   }
-  hipLaunchKernelGGL(k_mt_emit, dim3(mt_grid_tab(n)), dim3(256), 0, c->stream, src, dst, (const int64_t*)val, n,
+  hipLaunchKernelGGL(k_mt_emit, dim3(tab_grid_tab(n)), dim3(256), 0, c->stream, src, dst, (const int64_t*)val, n,
                      (const uint64_t*)nev, (const uint64_t*)pos, (const long long*)c->ts[8].p, o, t->meta);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, MT_META));
   t->matched += c->host_small[8 + MT_DCNT];
   t->total_weight += c->host_small[8 + MT_DW];
   t->records += n;
@@ -899,10 +855,10 @@ gs_status gs_match_export(gs_ctx* c, const gs_match* t, gs_edge_out* out) {
   unsigned long long* keys = c->ts[0].as<unsigned long long>();
   int64_t *es = c->ts[2].as<int64_t>(), *ed = c->ts[3].as<int64_t>(), *ew = c->ts[4].as<int64_t>();
   GS_HIP(hipMemsetAsync(t->meta + MT_PEND, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_mt_dump, dim3(mt_grid(t->cap + 1)), dim3(256), 0, c->stream, table_of(t), keys, c->ts[1].as<uint32_t>(),
+  hipLaunchKernelGGL(k_mt_dump, dim3(tab_grid(t->cap + 1)), dim3(256), 0, c->stream, table_of(t), keys, c->ts[1].as<uint32_t>(),
                      es, ed, ew, M);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, MT_META));
   if (c->host_small[8 + MT_PEND] != M)
     return set_error(c, GS_EDEVICE, "matching state: %llu edges in the table, %llu expected",
                      (unsigned long long)c->host_small[8 + MT_PEND], (unsigned long long)M);
@@ -910,7 +866,7 @@ gs_status gs_match_export(gs_ctx* c, const gs_match* t, gs_edge_out* out) {
   // ascending src = ascending (src ^ sign bit) as unsigned
   Sorted s;
   GS_TRY(sort_buffer(c, (const uint64_t*)keys, c->ts[1].p, M, &s, 64, 4));
-  hipLaunchKernelGGL(k_mt_gather, dim3(mt_grid(M)), dim3(256), 0, c->stream, (const uint32_t*)s.vals, M, (const int64_t*)es,
+  hipLaunchKernelGGL(k_mt_gather, dim3(tab_grid(M)), dim3(256), 0, c->stream, (const uint32_t*)s.vals, M, (const int64_t*)es,
                      (const int64_t*)ed, (const int64_t*)ew, os, od, ow);
   GS_HIP(hipGetLastError());
   if (direct) return GS_OK;
@@ -940,12 +896,12 @@ gs_status gs_match_import(gs_ctx* c, gs_match* t, const gs_edge_batch* rows) {
   GS_TRY(insert_batch(c, t, src, dst, n, nullptr));
   const uint32_t *su = c->ts[0].as<uint32_t>(), *sv = c->ts[1].as<uint32_t>();
   const uint32_t epoch = ++t->epoch;
-  const dim3 g(mt_grid_tab(n)), bl(256);
+  const dim3 g(tab_grid_tab(n)), bl(256);
   hipLaunchKernelGGL(k_mt_import_claim, g, bl, 0, c->stream, table_of(t), n, su, sv, epoch);
   GS_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mt_import_check, g, bl, 0, c->stream, table_of(t), n, su, sv, epoch);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, MT_META));
   if (c->host_small[8 + MT_ERR]) {
     GS_HIP(hipMemsetAsync(t->meta + MT_ERR, 0, 8, c->stream));   // no word of the refused rows stays behind
     return set_error(c, GS_EINVAL, "gs_match_import: two rows share an endpoint");
@@ -954,7 +910,7 @@ gs_status gs_match_import(gs_ctx* c, gs_match* t, const gs_edge_batch* rows) {
   t->broken = true;
   hipLaunchKernelGGL(k_mt_import_write, g, bl, 0, c->stream, table_of(t), n, su, sv, (const int64_t*)val);
   GS_HIP(hipGetLastError());
-  GS_TRY(read_meta(c, t));
+  GS_TRY(tab_read_meta(c, t->meta, MT_META));
   t->matched = n;
   t->records = n;
   t->total_weight = c->host_small[8 + MT_DW];

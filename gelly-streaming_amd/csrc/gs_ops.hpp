@@ -27,7 +27,8 @@ __host__ __device__ inline uint32_t owner_of(int64_t v, uint32_t nparts) {
   return (uint32_t)(((x >> 32) * (uint64_t)nparts) >> 32);
 }
 
-// the murmur3 finaliser: the slot hash of the device-resident tables (gs_continuous.hip, gs_distinct.hip)
+// the murmur3 finaliser: the slot hash of the device-resident tables (gs_table.hpp's tab_claim / tab_lookup for the
+// id-keyed ones, gs_distinct.hip, gs_trisample.hip)
 __device__ __forceinline__ unsigned long long ct_hash(unsigned long long x) {
   x ^= x >> 33;
   x *= 0xff51afd7ed558ccdull;

@@ -902,22 +902,22 @@ class Engine:
         return v
 
 
-class ContinuousState:
-    """gs_cont: the state of one continuous operator of SimpleEdgeStream (include/gelly_hip.h, "continuous
-    streams") -- vertex -> records seen so far, in HBM across calls.  Feed it the stream in batches of any
-    size: the concatenated outputs depend only on the stream.  Columns are numpy arrays (results come back
-    as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
+class _DeviceState:
+    """What the device-resident states share: the engine, the library, the handle and its lifetime.  A subclass
+    names its C symbols: _DESTROY, and _SIZE / _CAPACITY where its getter fills two uint64."""
 
-    def __init__(self, engine: Engine, reserve_vertices: int = 0):
+    _DESTROY = _SIZE = _CAPACITY = None
+
+    def __init__(self, engine: "Engine", create: str, *args):
         self.engine = engine
         self._L = engine._L
         h = ctypes.c_void_p()
-        engine._check(self._L.gs_cont_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
+        engine._check(getattr(self._L, create)(engine.ctx, *args, ctypes.byref(h)))
         self.handle = h
 
     def close(self):
         if getattr(self, "handle", None):
-            self._L.gs_cont_destroy(self.handle)
+            getattr(self._L, self._DESTROY)(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -931,6 +931,23 @@ class ContinuousState:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _pair(self, fn: str):
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._check(getattr(self._L, fn)(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+
+class ContinuousState(_DeviceState):
+    """gs_cont: the state of one continuous operator of SimpleEdgeStream (include/gelly_hip.h, "continuous
+    streams") -- vertex -> records seen so far, in HBM across calls.  Feed it the stream in batches of any
+    size: the concatenated outputs depend only on the stream.  Columns are numpy arrays (results come back
+    as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
+
+    _DESTROY, _SIZE, _CAPACITY = "gs_cont_destroy", "gs_cont_size", "gs_cont_capacity"
+
+    def __init__(self, engine: Engine, reserve_vertices: int = 0):
+        super().__init__(engine, "gs_cont_create", int(reserve_vertices))
 
     def _run(self, call, b, dev, R, out):
         e = self.engine
@@ -963,15 +980,11 @@ class ContinuousState:
 
     def size(self):
         """gs_cont_size: (distinct vertices, records) seen so far."""
-        d, r = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_cont_size(self.handle, ctypes.byref(d), ctypes.byref(r)))
-        return d.value, r.value
+        return self._pair(self._SIZE)
 
     def capacity(self):
         """gs_cont_capacity: (slots of the table, doublings so far); load factor = size()[0] / slots."""
-        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_cont_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
-        return s.value, g.value
+        return self._pair(self._CAPACITY)
 
     def export(self, device: bool = False):
         """gs_cont_export: the checkpoint (vertices ascending, counts), numpy or (device=True) CUDA tensors."""
@@ -996,40 +1009,20 @@ class ContinuousState:
         self.engine._check(self._L.gs_cont_import(self.engine.ctx, self.handle, ctypes.byref(pb)))
 
 
-class DistinctState:
+class DistinctState(_DeviceState):
     """gs_distinct: the state of one SimpleEdgeStream.distinct() (include/gelly_hip.h, "distinct()") -- a hash
     set of the edges seen so far and their log in first-arrival order, in HBM across calls.  Feed it the stream
     in batches of any size: the concatenated outputs depend only on the stream.  Columns are numpy arrays
     (results come back as numpy) or CUDA tensors of the engine's device (results stay in HBM)."""
 
     MODES = {"keyed": L.GS_DISTINCT_KEYED, "instance": L.GS_DISTINCT_INSTANCE}
+    _DESTROY, _SIZE, _CAPACITY = "gs_distinct_destroy", "gs_distinct_size", "gs_distinct_capacity"
 
     def __init__(self, engine: Engine, mode: str = "keyed", reserve_edges: int = 0):
         if mode not in self.MODES:
             raise ValueError(f"mode: one of {sorted(self.MODES)}")
-        self.engine = engine
         self.mode = mode
-        self._L = engine._L
-        h = ctypes.c_void_p()
-        engine._check(self._L.gs_distinct_create(engine.ctx, self.MODES[mode], int(reserve_edges), ctypes.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.gs_distinct_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(engine, "gs_distinct_create", self.MODES[mode], int(reserve_edges))
 
     def edges(self, src, dst, val=None, out=None):
         """gs_distinct_edges: the edges of the batch never seen before, in arrival order, as (src, dst, val,
@@ -1057,15 +1050,11 @@ class DistinctState:
 
     def size(self):
         """gs_distinct_size: (distinct edges kept, records seen, duplicates included)."""
-        d, r = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_distinct_size(self.handle, ctypes.byref(d), ctypes.byref(r)))
-        return d.value, r.value
+        return self._pair(self._SIZE)
 
     def capacity(self):
         """gs_distinct_capacity: (slots of the table, doublings so far); load factor = size()[0] / slots."""
-        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_distinct_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
-        return s.value, g.value
+        return self._pair(self._CAPACITY)
 
     def export(self, device: bool = False):
         """gs_distinct_export: the checkpoint -- (src, dst) of the distinct edges in first-arrival order (the
@@ -1087,7 +1076,7 @@ class DistinctState:
         self.engine._check(self._L.gs_distinct_import(self.engine.ctx, self.handle, ctypes.byref(b)))
 
 
-class WeightedMatchingState:
+class WeightedMatchingState(_DeviceState):
     """gs_match: the matching of one CentralizedWeightedMatching mapper (include/gelly_hip.h,
     "CentralizedWeightedMatching") -- per vertex its partner, the edge's value and which end it is, in HBM across
     calls.  Feed it the stream in batches of any size: the concatenated events depend only on the stream.
@@ -1097,29 +1086,10 @@ class WeightedMatchingState:
     COLUMNS = ("type", "src", "dst", "val", "index")
     _DTYPES = {"type": np.uint8, "src": np.int64, "dst": np.int64, "val": np.int64, "index": np.int64}
 
+    _DESTROY, _CAPACITY = "gs_match_destroy", "gs_match_capacity"
+
     def __init__(self, engine: Engine, reserve_vertices: int = 0):
-        self.engine = engine
-        self._L = engine._L
-        h = ctypes.c_void_p()
-        engine._check(self._L.gs_match_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.gs_match_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(engine, "gs_match_create", int(reserve_vertices))
 
     def edges(self, src, dst, val, out=None, capacity: int = None, columns=COLUMNS):
         """gs_match_edges: the MatchingEvents of the batch in stream order as (type, src, dst, val, index) --
@@ -1172,9 +1142,7 @@ class WeightedMatchingState:
 
     def capacity(self):
         """gs_match_capacity: (slots of the vertex table, doublings so far)."""
-        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_match_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
-        return s.value, g.value
+        return self._pair(self._CAPACITY)
 
     def last_batch(self):
         """gs_match_last_batch: {rounds, block_iterations, pending_after: {1, 2, 4, 8: edges}} of the last batch."""
@@ -1202,7 +1170,7 @@ class WeightedMatchingState:
         self.engine._check(self._L.gs_match_import(self.engine.ctx, self.handle, ctypes.byref(b)))
 
 
-class AssignComponentsState:
+class AssignComponentsState(_DeviceState):
     """gs_assign: the partition of one AssignComponents mapper (include/gelly_hip.h, "AssignComponents") -- per
     vertex the smallest vertex of its component, in HBM across calls.  Feed it the stream in batches of any size:
     the concatenated records depend only on the stream.  Columns are numpy arrays (results come back as numpy) or
@@ -1210,30 +1178,11 @@ class AssignComponentsState:
 
     _DTYPES = (np.int64, np.int64, np.uint32)
 
+    _DESTROY, _CAPACITY = "gs_assign_destroy", "gs_assign_capacity"
+
     def __init__(self, engine: Engine, reserve_vertices: int = 0):
-        self.engine = engine
-        self._L = engine._L
-        h = ctypes.c_void_p()
-        engine._check(self._L.gs_assign_create(engine.ctx, int(reserve_vertices), ctypes.byref(h)))
-        self.handle = h
+        super().__init__(engine, "gs_assign_create", int(reserve_vertices))
         self.last_records = 0
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.gs_assign_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def edges(self, src, dst, out=None, capacity: int = None):
         """gs_assign_edges: the records of the batch as (vertex, label, edge), grouped by edge in arrival order
@@ -1274,9 +1223,7 @@ class AssignComponentsState:
 
     def capacity(self):
         """gs_assign_capacity: (slots of the vertex table, doublings so far)."""
-        s, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self.engine._check(self._L.gs_assign_capacity(self.handle, ctypes.byref(s), ctypes.byref(g)))
-        return s.value, g.value
+        return self._pair(self._CAPACITY)
 
     def last_batch(self):
         """gs_assign_last_batch: {rounds, merging_edges, records, live_after: {1, 2, 4, 8: edges}} of the last batch."""
@@ -1308,7 +1255,7 @@ class AssignComponentsState:
         self.engine._check(self._L.gs_assign_import(self.engine.ctx, self.handle, ctypes.byref(pb)))
 
 
-class TriangleSamplerState:
+class TriangleSamplerState(_DeviceState):
     """gs_trisample: `samples` samplers of the streaming triangle estimators (include/gelly_hip.h, "streaming
     triangle-count estimators"), their state in HBM across calls.  Feed it the stream in batches of any size:
     the concatenated records and the exported state depend only on the stream.  Columns are numpy arrays
@@ -1316,37 +1263,17 @@ class TriangleSamplerState:
 
     MODES = {"broadcast": L.GS_TRISAMPLE_BROADCAST, "incidence": L.GS_TRISAMPLE_INCIDENCE}
     TILE = L.GS_TRISAMPLE_TILE
+    _DESTROY = "gs_trisample_destroy"
 
     def __init__(self, engine: Engine, mode: str, samples: int, vertex_count: int, seed: int = 0, first_sampler: int = 0):
         if mode not in self.MODES:
             raise ValueError(f"mode: one of {sorted(self.MODES)}")
         if samples < 0 or vertex_count < 0 or first_sampler < 0:
             raise ValueError("samples, vertex_count and first_sampler are not negative")
-        self.engine = engine
         self.mode = mode
         self.samples = int(samples)
-        self._L = engine._L
-        h = ctypes.c_void_p()
-        engine._check(self._L.gs_trisample_create(engine.ctx, self.MODES[mode], int(samples), int(first_sampler),
-                                                  int(vertex_count), int(seed) & (2**64 - 1), ctypes.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.gs_trisample_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(engine, "gs_trisample_create", self.MODES[mode], int(samples), int(first_sampler),
+                         int(vertex_count), int(seed) & (2**64 - 1))
 
     def edges(self, src, dst, capacity: int = None):
         """gs_trisample_edges: the TriangleEstimate records of the batch as (edge counts, local beta sums), in

@@ -465,3 +465,34 @@ def test_triangles_self_pairs_exact_jdk_order(engine, oracle):
     assert engine.triangles(*(torch.from_numpy(x).cuda() for x in (s, d))) == (ex, w, has)
     w2, ex2, has2, flags = oracle.window_triangles_ref(s[:4000], d[:4000])
     assert flags and engine.triangles(s[:4000], d[:4000]) == (ex2, w2, has2)
+
+
+STATE_FACTORIES = {
+    "continuous": lambda e: e.continuous(),
+    "distinct": lambda e: e.distinct(),
+    "weighted_matching": lambda e: e.weighted_matching(),
+    "assign_components": lambda e: e.assign_components(),
+    "triangle_sampler": lambda e: e.triangle_sampler("broadcast", samples=4, vertex_count=8),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(STATE_FACTORIES))
+def test_device_state_lifecycle(engine, kind):
+    """Every device-resident state is a context manager over its handle: leaving the block destroys it, a second
+    close() does nothing, and a state dropped without close() is destroyed when it is collected, without raising."""
+    import gc
+
+    factory = STATE_FACTORIES[kind]
+    with factory(engine) as st:
+        assert st.handle and st.engine is engine
+    assert st.handle is None
+    st.close()
+    assert st.handle is None
+    dropped = factory(engine)
+    assert dropped.handle
+    dropped.__del__()                 # what the collector calls: it must not raise, and it closes
+    assert dropped.handle is None
+    del dropped
+    factory(engine)                   # never bound: dropped at once
+    gc.collect()
+    engine.synchronize()

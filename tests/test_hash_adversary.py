@@ -118,13 +118,12 @@ def test_home_tag_and_filter_bit_are_the_bits_they_name():
 # ---- the restatement is pinned to the sources ------------------------------------------------------------------
 CT_HASH_BODY = "x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33; return x;"
 PAIR_EXPR = "ct_hash(ct_hash((unsigned long long)A) ^ ((unsigned long long)B * 0x9e3779b97f4a7c15ull))"
-SLOT_FROM_LOW_BITS = {                       # file -> every way it takes a home slot from a hash
-    "gs_continuous.hip": [r"ct_hash\(id\) & t\.mask"],
-    "gs_matching.hip": [r"ct_hash\(id\) & t\.mask"],
-    "gs_assign.hip": [r"ct_hash\(id\) & t\.mask"],
-    "gs_distinct.hip": [r"slot = h & t\.mask"],
-    "gs_trisample.hip": [r"slot = \(uint32_t\)h & t\.mask"],
+SLOT_FROM_LOW_BITS = {                       # file -> (the mask's name, every way it takes a home slot from a hash)
+    "gs_table.hpp": (r"mask", [r"ct_hash\(id\) & mask"]),
+    "gs_distinct.hip": (r"t\.mask", [r"slot = h & t\.mask"]),
+    "gs_trisample.hip": (r"t\.mask", [r"slot = \(uint32_t\)h & t\.mask"]),
 }
+ID_KEYED = ["gs_continuous.hip", "gs_matching.hip", "gs_assign.hip"]   # they probe through gs_table.hpp alone
 WHO = "tests/hash_adversary.py restates this hash: change both, or its collision streams stop colliding"
 
 
@@ -160,11 +159,14 @@ def source_pins(csrc):
     pins.append(("ds_tag", _function_body(ds, r"unsigned long long ds_tag\(unsigned long long h\)"),
                  "return (h >> DS_TAG_SHIFT) << DS_TAG_SHIFT;"))
     pins.append(("the filter bit", len(re.findall(r"bit = \(uint32_t\)\(h >> \(64 - TS_FILTER_BITS\)\);", ts)), 2))
-    for fname, patterns in SLOT_FROM_LOW_BITS.items():
+    for fname, (mask, patterns) in SLOT_FROM_LOW_BITS.items():
         text = (csrc / fname).read_text()
-        masked = len(re.findall(r"(?<!\+ 1\) )& t\.mask", text))      # every `& t.mask` that is not a probe's step
+        masked = len(re.findall(r"(?<!\+ 1\) )& " + mask, text))      # every `& mask` that is not a probe's step
         found = sum(len(re.findall(p, text)) for p in patterns)
         pins.append((f"home slots from the low hash bits ({fname})", (found > 0, found), (True, masked)))
+    for fname in ID_KEYED:
+        masked = len(re.findall(r"(?<!\+ 1\) )& t\.mask", (csrc / fname).read_text()))
+        pins.append((f"no home slot of its own: the probes are gs_table.hpp's ({fname})", masked, 0))
     return pins
 
 
@@ -186,11 +188,13 @@ def test_restatement_is_pinned_to_the_sources():
     ("gs_trisample.hip", "(unsigned long long)b * 0x9e3779b97f4a7c15ull", "(unsigned long long)b * 0x9e3779b97f4a7c13ull"),
     ("gs_distinct.hip", "DS_TAG_SHIFT = 41;", "DS_TAG_SHIFT = 40;"),
     ("gs_trisample.hip", "TS_FILTER_BITS = 19;", "TS_FILTER_BITS = 18;"),
-    ("gs_assign.hip", "unsigned long long s = ct_hash(id) & t.mask;", "unsigned long long s = (ct_hash(id) >> 7) & t.mask;"),
+    ("gs_table.hpp", "unsigned long long s = ct_hash(id) & mask;", "unsigned long long s = (ct_hash(id) >> 7) & mask;"),
+    ("gs_matching.hip", "  return (uint32_t)tab_claim<sizeof(MtSlot) / 8>(&t.slots->id, t.mask, id, fresh);",
+     "  unsigned long long s = ct_hash(id) & t.mask;\n  return (uint32_t)s;"),
     ("gs_distinct.hip", "slot = h & t.mask", "slot = (h >> 20) & t.mask"),
 ])
 def test_an_edited_copy_of_the_sources_fails_the_pin(tmp_path, fname, old, new):
-    for f in ["gs_ops.hpp"] + list(SLOT_FROM_LOW_BITS):
+    for f in ["gs_ops.hpp"] + list(SLOT_FROM_LOW_BITS) + ID_KEYED:
         text = (CSRC / f).read_text()
         if f == fname:
             assert old in text
