@@ -55,7 +55,7 @@ gs_status launch_info(gs_ctx* c, const int64_t* src, const int64_t* dst, uint64_
   GS_HIP(hipMemsetAsync(sm + SM_BK_MM, 0, 32, c->stream));
   GS_HIP(hipMemsetAsync(hist, 0, BK_MAXB * 4, c->stream));
   const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 4095) / 4096, 1024));
+  const unsigned grid = grid_for(n, 4096, 1024);
   if (vec)
     hipLaunchKernelGGL((k_bk_info<DIR, true>), dim3(grid), dim3(BK_INFO_BLOCK), 0, c->stream, src, dst, n, base, S,
                        (uint32_t)BK_MAXB, hist, (unsigned long long*)(sm + SM_BK_MM));
@@ -223,7 +223,7 @@ gs_status bucket_accumulate(gs_ctx* c, Src rs, uint64_t R, uint32_t nb, int64_t 
                        (const uint32_t*)(meta + BkMeta::BCOUNT), nb, (const uint32_t*)st.k, base, e.nparts, e.cnt, e.wide,
                        mm, (const uint32_t*)(sm + SM_TIMEOUT), (const unsigned long long*)(sm + SM_BK_ESC),
                        (unsigned long long*)(sm + SM_BK_X));
-    hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(1024), 0, c->stream, e.cnt, nb * BK_OE_SLICES * e.nparts,
+    hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, e.cnt, nb * BK_OE_SLICES * e.nparts,
                        nb * BK_OE_SLICES, e.nparts, e.totals,
                        (unsigned long long*)(sm + SM_BK_MM + 24));
     hipLaunchKernelGGL((k_bk_owner_emit<P>), dim3(nb, BK_OE_SLICES), dim3(256), 0, c->stream, (const uint32_t*)(meta + BkMeta::BSTART),

@@ -567,26 +567,6 @@ __global__ __launch_bounds__(BK_INFO_BLOCK) void k_bk_info(const int64_t* __rest
   }
 }
 
-// block-wide exclusive scan of one u32 per thread (BLOCK = BK_PLAN_BLOCK); returns the total
-// (1024-thread blocks only: it reads BK_PLAN_BLOCK / WAVE wave sums; block_excl_scan<BLOCK> for others)
-__device__ __forceinline__ uint32_t bk_block_scan(uint32_t x, uint32_t* s_w, uint32_t& total) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  constexpr int NW = BK_PLAN_BLOCK / WAVE;
-  const uint32_t inc = wave_inclusive_sum(x);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) {
-    const uint32_t v = s_w[i];
-    off += i < w ? v : 0u;
-    tot += v;
-  }
-  __syncthreads();
-  total = tot;
-  return off + inc - x;
-}
-
 constexpr int BK_LPT_CLASSES = 64;
 // the work items of buckets 2 tid and 2 tid + 1 (c0, c1 records; one block of BK_PLAN_BLOCK threads): a bucket
 // of cnt records is split into ceil(cnt / item_recs) items; multi-item buckets get consecutive slabs.  A bucket
@@ -604,9 +584,9 @@ __device__ __forceinline__ uint32_t bk_plan_items(uint32_t c0, uint32_t c1, uint
   const uint32_t lk = max(1u, inline_k);   // more items than this: a launched merge
   const uint32_t g0 = i0 > lk ? 1u : 0u, g1 = i1 > lk ? 1u : 0u;
   uint32_t n_items, n_slabs, n_multi;
-  bk_block_scan(i0 + i1, s_w, n_items);
-  const uint32_t slab0 = bk_block_scan(m0 + m1, s_w, n_slabs);
-  const uint32_t mb0 = bk_block_scan(g0 + g1, s_w, n_multi);
+  block_exclusive_sum<BK_PLAN_BLOCK>(i0 + i1, s_w, n_items);
+  const uint32_t slab0 = block_exclusive_sum<BK_PLAN_BLOCK>(m0 + m1, s_w, n_slabs);
+  const uint32_t mb0 = block_exclusive_sum<BK_PLAN_BLOCK>(g0 + g1, s_w, n_multi);
   // claim order: largest items first (k_bk_accum's workgroups take items from a counter, so the small
   // ones fill the gaps at the end instead of a large one starting last): a counting sort over
   // BK_LPT_CLASSES size classes, descending; the order within a class is free
@@ -701,7 +681,7 @@ static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_bk_plan(const uint32_t
     if (c1) atomicAdd(&s_dh[p][(b1 >> (p * w)) & dmask], c1);
   }
   uint32_t total;
-  const uint32_t start0 = bk_block_scan(c0 + c1, s_w, total);
+  const uint32_t start0 = block_exclusive_sum<BK_PLAN_BLOCK>(c0 + c1, s_w, total);
   if (spec) {   // the occupied buckets (the next window's predicted range)
     __shared__ uint32_t s_lo, s_hi;
     if (tid == 0) {
@@ -1001,7 +981,7 @@ __global__ __launch_bounds__(DP_BLOCK) void k_dp_scatter(BaseSrc<V, DIR, PAY> es
     __syncthreads();
     const uint32_t c0 = b0 < nbp ? s_cnt[b0] : 0u, c1 = b1 < nbp ? s_cnt[b1] : 0u;
     uint32_t total;
-    const uint32_t st0 = bk_block_scan(c0 + c1, s_w, total);
+    const uint32_t st0 = block_exclusive_sum<DP_BLOCK>(c0 + c1, s_w, total);
     // unconditional: entries past nbp are never read, and a branch here would make the compiler
     // wait for every outstanding load (the prefetch) before the offsets it guards
     s_cnt[b0] = st0;
@@ -1144,7 +1124,7 @@ void k_dp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
   __syncthreads();
   const uint32_t c0 = b0 < nbp ? s_cnt[b0] : 0u, c1 = b1 < nbp ? s_cnt[b1] : 0u;
   uint32_t total;
-  const uint32_t st0 = bk_block_scan(c0 + c1, s_w, total);
+  const uint32_t st0 = block_exclusive_sum<DP_BLOCK>(c0 + c1, s_w, total);
   s_cnt[b0] = st0;   // unconditional: entries past nbp are never read
   s_delta[b0] = o0 - st0;
   s_cnt[b1] = st0 + c0;
@@ -1228,7 +1208,7 @@ static __global__ __launch_bounds__(BK_PLAN_BLOCK) void k_sp_regions(const uint3
   };
   const uint32_t c0 = cap(b0), c1 = cap(b1);
   uint32_t total;
-  const uint32_t s0 = bk_block_scan(c0 + c1, s_w, total);
+  const uint32_t s0 = block_exclusive_sum<BK_PLAN_BLOCK>(c0 + c1, s_w, total);
   if (b0 < nb) bucket_start[b0] = s0;
   if (b1 < nb) bucket_start[b1] = s0 + c0;
   // segment x of bucket b: [lo, hi); its cursor starts at lo
@@ -1308,25 +1288,6 @@ __host__ __device__ constexpr uint32_t spk_tile_edges() {
 template <int DIR>
 __host__ __device__ inline uint32_t spk_grid(uint64_t n) {
   return (uint32_t)((n / spk_tile_edges<DIR>() + 7) / 8 * 8 + 1);
-}
-
-// block-wide exclusive scan of one u32 per thread (BLOCK threads); returns the total
-template <int BLOCK>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_w, uint32_t& total) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  constexpr int NW = BLOCK / WAVE;
-  const uint32_t inc = wave_inclusive_sum(x);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) {
-    const uint32_t v = s_w[i];
-    off += i < w ? v : 0u;
-    tot += v;
-  }
-  total = tot;
-  return off + inc - x;
 }
 
 // The bucket a thread reserves (k of its BPT): k-major (tid + k * BLOCK), so one wave-instruction of
@@ -1450,7 +1411,9 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
 #pragma unroll
   for (int k = 0; k < BPT; ++k) ob[k] = cb[k] ? atomicAdd(&cursor[SP_BK(k)], cb[k]) : 0u;
   uint32_t total;
-  uint32_t st = block_excl_scan<BLOCK>(sum, s_w, total);   // total: records in the predicted range
+  // total: records in the predicted range.  No trailing barrier: this is the block's only write of s_w, and the
+  // barrier after the s_run stores below follows its reads
+  uint32_t st = block_exclusive_sum<BLOCK, uint32_t, false>(sum, s_w, total);
   // A run that does not fit its segment goes to the trash area [trash, trash + TILE) past every region,
   // at its tile position (nothing reads the trash).
   // Every slot carries its record's global position, so the store loop needs no table lookup
@@ -1655,7 +1618,9 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 #pragma unroll
   for (int k = 0; k < BPT; ++k) ob[k] = cb[k] ? atomicAdd(&cursor[SP_BK(k)], cb[k]) : 0u;
   uint32_t total;
-  uint32_t st = block_excl_scan<BLOCK>(sum, s_w, total);   // (bk_block_scan assumes 1024 threads)
+  // no trailing barrier: this is the block's only write of s_w, and the barrier after the s_cnt stores below
+  // follows its reads
+  uint32_t st = block_exclusive_sum<BLOCK, uint32_t, false>(sum, s_w, total);
   uint32_t sb[BPT];
 #pragma unroll
   for (int k = 0; k < BPT; ++k) {

@@ -378,7 +378,6 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
   static const int giant_env = getenv("GS_CC_GIANT") ? atoi(getenv("GS_CC_GIANT")) : 1;
   const bool two_phase = sample_env > 1 && (sample_env & (sample_env - 1)) == 0 && N >= 65536;
   const uint32_t smask = two_phase ? (uint32_t)sample_env - 1 : 0;
-  auto grid = [](uint64_t x, uint64_t cap) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((x + 255) / 256, cap)); };
 
   // the union-find over V words: the hooks of one phase are launched by hook(phase, table).  One pass: phase 0 with
   // sample mask 0, which is every constraint.  Two-phase: the sampled constraints, a full compression (every vertex
@@ -393,7 +392,7 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
     const uint32_t* gtab = nullptr;
     hook(0, gtab);
     if (!two_phase) return GS_OK;
-    hipLaunchKernelGGL(k_uf_compress<F>, dim3(grid(V, 16384)), dim3(256), 0, c->stream, w, V, mark);
+    hipLaunchKernelGGL(k_uf_compress<F>, dim3(grid_for(V, 256, 16384)), dim3(256), 0, c->stream, w, V, mark);
     if (giant_env && ne >= 1024) {
       const size_t words = ((size_t)V * F::TABLE_BITS + 31) / 32;
       GS_TRY(ensure(c, c->aux, words * 4 + 64));
@@ -401,7 +400,7 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
       uint32_t* giant = t + words;
       hipLaunchKernelGGL(k_cc_giant<F::SHIFT>, dim3(1), dim3(1024), 0, c->stream, ga, gat, ne, key_xor, (const uint32_t*)w,
                          giant);
-      hipLaunchKernelGGL(k_uf_table<F>, dim3(grid(words, 16384)), dim3(256), 0, c->stream, (const uint32_t*)w, V,
+      hipLaunchKernelGGL(k_uf_table<F>, dim3(grid_for(words, 256, 16384)), dim3(256), 0, c->stream, (const uint32_t*)w, V,
                          (const uint32_t*)giant, t);
       gtab = t;
     }
@@ -457,7 +456,7 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
 
   // 2a. ids spanning <= CC_DIRECT_BITS bits: the union-find over the ids themselves (no relabel sort)
   for (const Seg& g : seg)
-    if (g.n) hipLaunchKernelGGL(k_cc_mask, dim3(grid(g.n, 8192)), dim3(256), 0, c->stream, g.a, g.b, g.n, k0p, dmask);
+    if (g.n) hipLaunchKernelGGL(k_cc_mask, dim3(grid_for(g.n, 256, 8192)), dim3(256), 0, c->stream, g.a, g.b, g.n, k0p, dmask);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(c->host_small + 12, dmask, 8, hipMemcpyDeviceToHost, c->stream));
   GS_HIP(hipMemcpyAsync(c->host_small + 13, k0p, 8, hipMemcpyDeviceToHost, c->stream));
@@ -473,14 +472,14 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
     GS_TRY(ensure(c, c->rl[3], (size_t)V * 8 + 8));
     uint32_t* w = c->cc[2].as<uint32_t>();
     uint8_t* mark = c->out_b.as<uint8_t>();
-    const unsigned gv = grid(V, 16384);
+    const unsigned gv = grid_for(V, 256, 16384);
     hipLaunchKernelGGL(k_uf_init<F>, dim3(gv), dim3(256), 0, c->stream, w, V);
     GS_HIP(hipMemsetAsync(mark, 0, V, c->stream));
     hipEventRecord(c->ev[1], c->stream);
     GS_TRY(unions(w, V, mark, big.a, nullptr, big.n, key_xor, [&](int phase, const uint32_t* gtab) {
       for (const Seg& g : seg)
         if (g.n)
-          hipLaunchKernelGGL((k_uf_hook<F, true>), dim3(grid(g.n, 8192)), dim3(256), 0, c->stream, g.a, g.b, g.n, key_xor, w, mark,
+          hipLaunchKernelGGL((k_uf_hook<F, true>), dim3(grid_for(g.n, 256, 8192)), dim3(256), 0, c->stream, g.a, g.b, g.n, key_xor, w, mark,
                              smask, phase, gtab, (const uint32_t*)nullptr, g.signs, g.n, fail);
     }));
     hipLaunchKernelGGL(k_uf_compress<F>, dim3(gv), dim3(256), 0, c->stream, w, V, mark);
@@ -503,7 +502,7 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
   }
   // 2b. compact ids: the window's edges appended to the state's rows (one edge list for the relabel sort; row e
   //     keeps its position, so rows [0, m) take their d from the state's signs)
-  if (n) hipLaunchKernelGGL(k_cc_concat, dim3(grid(n, 8192)), dim3(256), 0, c->stream, src, dst, n, A + m, Bc + m);
+  if (n) hipLaunchKernelGGL(k_cc_concat, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c->stream, src, dst, n, A + m, Bc + m);
   const int64_t *ca, *cb, *uniq;
   uint64_t U = 0;
   GS_TRY(relabel_endpoints(c, A, Bc, N, &ca, &cb, &uniq, &U));
@@ -514,11 +513,11 @@ static gs_status uf_window(gs_ctx* c, const UfOp& op, const gs_edge_batch* b, co
   GS_TRY(ensure(c, c->cc[2], U * 4 + 4));
   uint32_t* w = c->cc[2].as<uint32_t>();
   const uint32_t* at = c->rl[4].as<uint32_t>();
-  const unsigned gu = grid(U, 16384);
+  const unsigned gu = grid_for(U, 256, 16384);
   hipLaunchKernelGGL(k_uf_init<F>, dim3(gu), dim3(256), 0, c->stream, w, (uint32_t)U);
   if (F::SIGNED) GS_HIP(hipMemsetAsync(fail, 0, 4, c->stream));   // (the relabel sort shares the small buffer)
   GS_TRY(unions(w, (uint32_t)U, nullptr, nullptr, at, N, 0, [&](int phase, const uint32_t* gtab) {
-    hipLaunchKernelGGL((k_uf_hook<F, false>), dim3(grid(N, 16384)), dim3(256), 0, c->stream, (const int64_t*)nullptr,
+    hipLaunchKernelGGL((k_uf_hook<F, false>), dim3(grid_for(N, 256, 16384)), dim3(256), 0, c->stream, (const int64_t*)nullptr,
                        (const int64_t*)nullptr, N, 0ull, w, (uint8_t*)nullptr, smask, phase, gtab, at, S, m, fail);
   }));
   GS_HIP(hipGetLastError());

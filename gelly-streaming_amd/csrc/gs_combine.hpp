@@ -270,21 +270,16 @@ __global__ __launch_bounds__(BLOCK) void k_onesweep_combine(Src src, K* __restri
                                                              const uint32_t* __restrict__ digit_base,
                                                              uint32_t* __restrict__ table,
                                                              unsigned long long* __restrict__ total) {
-  __shared__ uint32_t ws[4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  __shared__ uint32_t ws[RADIX / WAVE];
+  const int tid = threadIdx.x;
   const uint32_t base = digit_base[tid];
   const uint32_t end = (uint32_t)g_value(status[(uint64_t)last_tile * RADIX + tid]);
-  const uint32_t len = end - base;
-  const uint32_t inc = wave_inclusive_sum(len);
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  uint32_t off = 0;
-  for (int i = 0; i < w; ++i) off += ws[i];
+  uint32_t all;
   table[tid] = base;
-  table[RADIX + tid] = off + inc - len;
+  table[RADIX + tid] = block_exclusive_sum<RADIX>(end - base, ws, all);
   if (tid == RADIX - 1) {
-    table[2 * RADIX] = off + inc;
-    *total = off + inc;
+    table[2 * RADIX] = all;
+    *total = all;
   }
 }
 

@@ -55,6 +55,79 @@ __device__ __forceinline__ uint64_t wave_or(uint64_t x) {
   return x;
 }
 
+// the wave's total, in every lane
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, WAVE);
+  return x;
+}
+
+// The block-wide exclusive scan of one value per thread: returns the sum of x over the threads below this one
+// and sets `total` to the sum over the whole block, in every thread (an inclusive result is the return value + x).
+//  - BLOCK is the launch's thread count (one-dimensional): exactly BLOCK / WAVE wave totals are written and read,
+//    so a BLOCK that is not the launch's reads words nobody wrote, or misses waves;
+//  - every thread of the block calls it, from uniform control flow: there is one barrier between the wave totals'
+//    stores and their loads, and with RESYNC one more after the loads, so that s_w (BLOCK / WAVE words of LDS)
+//    may be written again at once, by the next call for instance;
+//  - with RESYNC = false the caller names the later barrier that every thread passes before s_w is written again.
+template <int BLOCK, typename T, bool RESYNC = true>
+__device__ __forceinline__ T block_exclusive_sum(T x, T* s_w, T& total) {
+  static_assert(BLOCK % WAVE == 0 && BLOCK <= 1024, "whole waves, one workgroup");
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  constexpr int NW = BLOCK / WAVE;
+  const T inc = wave_inclusive_sum(x);
+  if (lane == 63) s_w[w] = inc;
+  __syncthreads();
+  T off = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const T v = s_w[i];
+    off += i < w ? v : T(0);
+    tot += v;
+  }
+  if constexpr (RESYNC) __syncthreads();
+  total = tot;
+  return off + inc - x;
+}
+
+// ---- one block scans an array in place (exclusive), SCAN_BLOCK threads ------------------------------------
+// Two traversals, both kept: a contiguous chunk per thread (the class-major and owner-major count tables, a few
+// thousand words read twice by the same thread), and coalesced SCAN_BLOCK-wide chunks with a carry (the tile
+// counts of the text parser and of the u64 scan).  Neither has been measured on the other's inputs.
+constexpr int SCAN_BLOCK = 1024;
+
+// a[0 .. n) in place, thread t owning the ceil(n / SCAN_BLOCK) elements from t * ceil(n / SCAN_BLOCK); returns the
+// total.  A thread's stores are ordered against the other threads' loads only by the caller's next barrier.
+__device__ __forceinline__ uint32_t block_scan_array_chunked(uint32_t* a, uint32_t n, uint32_t* s_w) {
+  const uint32_t per = (n + SCAN_BLOCK - 1) / SCAN_BLOCK, lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
+  uint32_t sum = 0, total;
+  for (uint32_t i = lo; i < hi; ++i) sum += a[i];
+  uint32_t run = block_exclusive_sum<SCAN_BLOCK>(sum, s_w, total);
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint32_t x = a[i];
+    a[i] = run;
+    run += x;
+  }
+  return total;
+}
+
+// a[0 .. n) in place and the total at a[n]: chunk after chunk of SCAN_BLOCK elements, the carry in a register
+template <typename T>
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_chunks(T* __restrict__ a, uint32_t n) {
+  __shared__ T s_w[SCAN_BLOCK / WAVE];
+  T carry = 0;
+  for (uint32_t base = 0; base < n; base += SCAN_BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    const T x = i < n ? a[i] : T(0);
+    T total;
+    const T below = block_exclusive_sum<SCAN_BLOCK>(x, s_w, total);
+    if (i < n) a[i] = carry + below;
+    carry += total;
+  }
+  if (threadIdx.x == 0) a[n] = carry;
+}
+
 // ---- look-back granules: [63:62] flag, [61:40] epoch, [39:0] value -------------------------
 constexpr uint64_t FLAG_AGG = 1ull, FLAG_INC = 2ull;
 constexpr uint32_t EPOCH_BITS = 22;

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(OW_BLOCK) void k_owner_scatter(const int64_t* __res
   __shared__ uint8_t s_own[OW_TILE];
   __shared__ uint32_t s_w[OW_BLOCK / WAVE];
   __shared__ uint32_t s_lo[MAXP + 1];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const uint64_t base = (uint64_t)blockIdx.x * OW_TILE;
   const uint32_t nt = (uint32_t)min<uint64_t>(OW_TILE, U - base);
 #pragma unroll
@@ -131,18 +131,9 @@ __global__ __launch_bounds__(OW_BLOCK) void k_owner_scatter(const int64_t* __res
   }
   if (tid == 0) s_lo[0] = 0;
   for (uint32_t o = 0; o < nparts; ++o) {   // exclusive scan of owner o's counts over threads; its tile total
-    const uint32_t x = s_r[o][tid];
-    const uint32_t inc = wave_inclusive_sum(x);
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-    for (int k = 0; k < OW_BLOCK / WAVE; ++k) {
-      pre += k < w ? s_w[k] : 0u;
-      tot += s_w[k];
-    }
-    s_r[o][tid] = (uint16_t)(pre + inc - x);
+    uint32_t tot;
+    s_r[o][tid] = (uint16_t)block_exclusive_sum<OW_BLOCK>((uint32_t)s_r[o][tid], s_w, tot);
     if (tid == 0) s_lo[o + 1] = tot;   // (turned into starts below)
-    __syncthreads();
   }
   if (tid == 0)
     for (uint32_t o = 0; o < nparts; ++o) s_lo[o + 1] += s_lo[o];
@@ -204,7 +195,7 @@ gs_status owner_partition_dev(gs_ctx* c, const int64_t* keys, const void* vals, 
     hipLaunchKernelGGL(k_owner_count<8>, dim3(tiles), dim3(OW_BLOCK), 0, c->stream, keys, U, nparts, tiles, cnt, wide);
   else
     hipLaunchKernelGGL(k_owner_count<OW_MAXP>, dim3(tiles), dim3(OW_BLOCK), 0, c->stream, keys, U, nparts, tiles, cnt, wide);
-  hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(1024), 0, c->stream, cnt, tiles * nparts, tiles, nparts, totals,
+  hipLaunchKernelGGL(k_owner_scan, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, cnt, tiles * nparts, tiles, nparts, totals,
                      nullptr);
   auto launch = [&](auto vtag, auto ptag, auto ttag) {
     using V = decltype(vtag);

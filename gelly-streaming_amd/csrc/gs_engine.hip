@@ -122,11 +122,6 @@ gs_status stage_batch(gs_ctx* c, const gs_edge_batch* b, const int64_t** src, co
   return GS_OK;
 }
 
-static inline unsigned grid_for(uint64_t n, unsigned per_block, unsigned cap) {
-  const uint64_t g = (n + per_block - 1) / per_block;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 template <int DIR>
 static gs_status launch_keyinfo(gs_ctx* c, const int64_t* src, const int64_t* dst, uint64_t n, bool mask_only = false) {
   char* sm = c->small.as<char>();

@@ -95,10 +95,7 @@ __global__ __launch_bounds__(256) void k_gen_zipf(const uint64_t* __restrict__ c
   }
 }
 
-static unsigned gen_grid(uint64_t n) {
-  uint64_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
+static unsigned gen_grid(uint64_t n) { return grid_for(n, 256, 8192); }
 
 }  // namespace gs
 

@@ -45,42 +45,15 @@ constexpr int XS_BLOCK = 256, XS_ITEMS = 16, XS_TILE = XS_BLOCK * XS_ITEMS;
 __global__ __launch_bounds__(XS_BLOCK) void k_xs_tiles(const uint64_t* __restrict__ in, uint64_t n,
                                                        uint64_t* __restrict__ tile_sum) {
   __shared__ uint64_t ws[XS_BLOCK / 64];
-  uint64_t t = 0;
+  uint64_t t = 0, total;
   const uint64_t base = (uint64_t)blockIdx.x * XS_TILE;
 #pragma unroll
   for (int j = 0; j < XS_ITEMS; ++j) {
     const uint64_t p = base + (uint64_t)j * XS_BLOCK + threadIdx.x;
     if (p < n) t += in[p];
   }
-  t = wave_inclusive_sum(t);
-  if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int w = 0; w < XS_BLOCK / 64; ++w) s += ws[w];
-    tile_sum[blockIdx.x] = s;
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_xs_top(uint64_t* __restrict__ tile_sum, uint32_t ntiles) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < ntiles; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint64_t x = i < ntiles ? tile_sum[i] : 0ull;
-    const uint64_t inc = wave_inclusive_sum(x);
-    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t off = carry;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += ws[w];
-    if (i < ntiles) tile_sum[i] = off + inc - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = off + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile_sum[ntiles] = carry;
+  block_exclusive_sum<XS_BLOCK>(t, ws, total);
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(XS_BLOCK) void k_xs_apply(const uint64_t* __restrict__ in, uint64_t n,
@@ -95,11 +68,8 @@ __global__ __launch_bounds__(XS_BLOCK) void k_xs_apply(const uint64_t* __restric
     v[j] = (first + j < n) ? in[first + j] : 0ull;
     t += v[j];
   }
-  const uint64_t inc = wave_inclusive_sum(t);
-  if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  uint64_t off = tile_off[blockIdx.x] + inc - t;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += ws[w];
+  uint64_t total;
+  uint64_t off = tile_off[blockIdx.x] + block_exclusive_sum<XS_BLOCK>(t, ws, total);
 #pragma unroll
   for (int j = 0; j < XS_ITEMS; ++j) {
     if (first + j < n) out[first + j] = off;
@@ -1201,12 +1171,12 @@ gs_status xscan(gs_ctx* c, const uint64_t* in, uint64_t n, uint64_t* out) {
   GS_TRY(ensure(c, c->hs[HS_TILES], (size_t)(tiles + 1) * 8));
   uint64_t* ts = c->hs[HS_TILES].as<uint64_t>();
   hipLaunchKernelGGL(k_xs_tiles, dim3(tiles), dim3(XS_BLOCK), 0, c->stream, in, n, ts);
-  hipLaunchKernelGGL(k_xs_top, dim3(1), dim3(1024), 0, c->stream, ts, tiles);
+  hipLaunchKernelGGL(k_scan_chunks<uint64_t>, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, ts, tiles);
   hipLaunchKernelGGL(k_xs_apply, dim3(tiles), dim3(XS_BLOCK), 0, c->stream, in, n, (const uint64_t*)ts, out);
   return hip_check(c, hipGetLastError(), "exclusive scan");
 }
 
-static unsigned g256(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
+static unsigned g256(uint64_t n) { return grid_for(n, 256, 16384); }
 
 // Distinct neighbour sets of every vertex of an ALL window, in HashSet order.  Results in c->hs[...]:
 // HS_VKEYS[U] vertex IDs, HS_OFF[U+1] record offsets, HS_NBR[R] neighbours (arrival order),
@@ -1468,7 +1438,7 @@ template <typename OT>
 static gs_status cand_emit(gs_ctx* c, uint32_t S, uint64_t P0, uint64_t P1, OT* a, OT* b, uint8_t* f, int64_t idb = 0) {
   const uint64_t n = P1 - P0;
   if (n == 0) return GS_OK;
-  const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n + 4095) / 4096, 4096));
+  const uint64_t blocks = grid_for(n, 4096, 4096);
   const uint64_t waves = blocks * 4;
   const uint64_t per_wave = ((n + waves - 1) / waves + 255) / 256 * 256;
   // bit 0: the flag column 4-byte aligned; bit 1: a and b 16-byte aligned (the fast path's vector stores)

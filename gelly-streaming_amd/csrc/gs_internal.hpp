@@ -4,11 +4,18 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/gelly_hip.h"
 
 namespace gs {
+
+// blocks of a grid-stride launch over n items: per_block items each, at least one block, at most cap
+inline unsigned grid_for(uint64_t n, unsigned per_block, unsigned cap) {
+  const uint64_t g = (n + per_block - 1) / per_block;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
+}
 
 struct DevBuf {
   void* p = nullptr;

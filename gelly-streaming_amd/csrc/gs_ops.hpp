@@ -40,36 +40,16 @@ __device__ __forceinline__ unsigned long long ct_hash(unsigned long long x) {
 
 // one block: exclusive scan of cnt[0 .. n) (owner-major) in place; totals[o] = partials of owner o, *n_out
 // (optional) = all of them (gs_dist.hip's owner partition; the bucket path's owner-grouped emit)
-static __global__ __launch_bounds__(1024) void k_owner_scan(uint32_t* __restrict__ cnt, uint32_t n, uint32_t tiles,
-                                                            uint32_t nparts, unsigned long long* __restrict__ totals,
-                                                            unsigned long long* __restrict__ n_out) {
-  __shared__ uint32_t s_w[16];
-  __shared__ uint32_t s_tot;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint32_t per = (n + 1023) / 1024, a = min(n, tid * per), b = min(n, a + per);
-  uint32_t sum = 0;
-  for (uint32_t i = a; i < b; ++i) sum += cnt[i];
-  const uint32_t inc = wave_inclusive_sum(sum);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-  for (int i = 0; i < 16; ++i) {
-    off += i < w ? s_w[i] : 0u;
-    tot += s_w[i];
-  }
-  uint32_t run = off + inc - sum;
-  for (uint32_t i = a; i < b; ++i) {
-    const uint32_t x = cnt[i];
-    cnt[i] = run;
-    run += x;
-  }
-  if (tid == 0) {
-    s_tot = tot;
-    if (n_out) *n_out = tot;
-  }
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_owner_scan(uint32_t* __restrict__ cnt, uint32_t n, uint32_t tiles,
+                                                                  uint32_t nparts, unsigned long long* __restrict__ totals,
+                                                                  unsigned long long* __restrict__ n_out) {
+  __shared__ uint32_t s_w[SCAN_BLOCK / WAVE];
+  const int tid = threadIdx.x;
+  const uint32_t tot = block_scan_array_chunked(cnt, n, s_w);
+  if (tid == 0 && n_out) *n_out = tot;
   __syncthreads();
   if (tid < (int)nparts) {
-    const uint32_t lo = cnt[(uint64_t)tid * tiles], hi = tid + 1 < (int)nparts ? cnt[(uint64_t)(tid + 1) * tiles] : s_tot;
+    const uint32_t lo = cnt[(uint64_t)tid * tiles], hi = tid + 1 < (int)nparts ? cnt[(uint64_t)(tid + 1) * tiles] : tot;
     totals[tid] = hi - lo;
   }
 }
@@ -239,7 +219,7 @@ inline gs_status reduce_fused(gs_ctx* c, const Sorted& s, Out o, uint64_t* U) {
   GS_TRY(host_wait(c));
   const uint64_t parts = c->host_small[5];
   c->times.partials = parts;
-  const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((parts + 255) / 256, 8192));
+  const unsigned g = grid_for(parts, 256, 8192);
   hipLaunchKernelGGL((k_compact_runs<K, Acc>), dim3(g), dim3(256), 0, c->stream, c->part_k.as<K>(), c->part_a.as<Acc>(),
                      table, (uint32_t)parts, c->comp_k.as<K>(), c->comp_a.as<Acc>());
   GS_HIP(hipGetLastError());

@@ -76,11 +76,7 @@ __global__ __launch_bounds__(PR_BLOCK) void k_pr_count(const int64_t* __restrict
   }
 }
 
-uint32_t grid_for(const gs_ctx* c, uint64_t n) {
-  const uint64_t want = (n + PR_BLOCK - 1) / PR_BLOCK;
-  const uint64_t cap = (uint64_t)std::max(1, c->n_cu) * 16;
-  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-}
+uint32_t pr_grid(const gs_ctx* c, uint64_t n) { return grid_for(n, PR_BLOCK, 16u * std::max(1, c->n_cu)); }
 
 }  // namespace
 
@@ -118,7 +114,7 @@ extern "C" gs_status gs_window_count_candidates(gs_ctx* c, const gs_pair_batch* 
   GS_TRY(ensure(c, c->pr_small, 64));
   unsigned long long* mm = c->pr_small.as<unsigned long long>();
   GS_HIP(hipMemsetAsync(mm, 0, 64, c->stream));
-  const uint32_t grid = grid_for(c, n);
+  const uint32_t grid = pr_grid(c, n);
   hipLaunchKernelGGL(k_pr_minmax, dim3(grid), dim3(PR_BLOCK), 0, c->stream, a, b, n, mm);
   GS_HIP(hipGetLastError());
   uint64_t h[4];
@@ -148,7 +144,7 @@ extern "C" gs_status gs_window_count_candidates(gs_ctx* c, const gs_pair_batch* 
   gs_vertex_out go{c->pr_gk.as<int64_t>(), c->pr_gv.p, n, &U, GS_MEM_DEVICE, 0};
   GS_TRY(gs_window_reduce(c, &kb, GS_DIR_OUT, GS_OP_SUM, &go));
   GS_HIP(hipMemsetAsync(mm, 0, 16, c->stream));
-  hipLaunchKernelGGL(k_pr_count, dim3(grid_for(c, U)), dim3(PR_BLOCK), 0, c->stream, c->pr_gv.as<int64_t>(), U, mm);
+  hipLaunchKernelGGL(k_pr_count, dim3(pr_grid(c, U)), dim3(PR_BLOCK), 0, c->stream, c->pr_gv.as<int64_t>(), U, mm);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(h, mm, 16, hipMemcpyDeviceToHost, c->stream));
   GS_TRY(host_wait(c));

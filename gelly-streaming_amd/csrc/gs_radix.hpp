@@ -228,17 +228,11 @@ __global__ __launch_bounds__(256) void k_hist_bytes(const int64_t* __restrict__ 
 // hist[p][256] -> base[p][256] exclusive scans, one wave-parallel scan per pass (block = 256)
 [[maybe_unused]] static __global__ __launch_bounds__(256) void k_digit_base(const uint32_t* __restrict__ hist, uint32_t* __restrict__ base,
                                                     int passes) {
-  __shared__ uint32_t wsum[4];
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  __shared__ uint32_t wsum[RADIX / WAVE];
+  const int tid = threadIdx.x;
   for (int p = 0; p < passes; ++p) {
-    const uint32_t c = hist[p * RADIX + tid];
-    const uint32_t inc = wave_inclusive_sum(c);
-    if (l == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-    for (int i = 0; i < w; ++i) off += wsum[i];
-    base[p * RADIX + tid] = off + inc - c;
-    __syncthreads();
+    uint32_t total;
+    base[p * RADIX + tid] = block_exclusive_sum<RADIX>(hist[p * RADIX + tid], wsum, total);
   }
 }
 
@@ -283,16 +277,10 @@ __global__ __launch_bounds__(1 << DBITS) void k_digit_base_bits(const uint32_t* 
                                                                int passes) {
   constexpr int R = 1 << DBITS, NW = R / WAVE;
   __shared__ uint32_t wsum[NW];
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   for (int p = 0; p < passes; ++p) {
-    const uint32_t c = hist[p * R + tid];
-    const uint32_t inc = wave_inclusive_sum(c);
-    if (l == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-    for (int i = 0; i < w; ++i) off += wsum[i];
-    base[p * R + tid] = off + inc - c;
-    __syncthreads();
+    uint32_t total;
+    base[p * R + tid] = block_exclusive_sum<R>(hist[p * R + tid], wsum, total);
   }
 }
 

@@ -60,8 +60,8 @@ gs_status relabel_endpoints(gs_ctx* c, const int64_t* a, const int64_t* b, uint6
   GS_TRY(ensure(c, c->rl[5], R * 8));   // sorted distinct IDs
   GS_TRY(ensure(c, c->rl[6], n * 8 + 8));   // compact columns
   GS_TRY(ensure(c, c->rl[7], n * 8 + 8));
-  const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192));
-  const unsigned gR = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((R + 255) / 256, 8192));
+  const unsigned g = grid_for(n, 256, 8192);
+  const unsigned gR = grid_for(R, 256, 8192);
   hipLaunchKernelGGL(k_rl_keys, dim3(g), dim3(256), 0, c->stream, a, b, n, c->rl[0].as<uint64_t>(),
                      c->rl[1].as<uint32_t>());
   GS_HIP(hipGetLastError());
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(256) void k_rl_map(int64_t* __restrict__ ca, int64_
 gs_status relabel_to_global(gs_ctx* c, const int64_t* loc, uint64_t nloc, const int64_t* G, uint64_t ng, uint32_t* map,
                             int64_t* ca, int64_t* cb, uint64_t n) {
   if (!n) return GS_OK;
-  const unsigned gl = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nloc + 255) / 256, 8192));
-  const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192));
+  const unsigned gl = grid_for(nloc, 256, 8192);
+  const unsigned g = grid_for(n, 256, 8192);
   hipLaunchKernelGGL(k_rl_rank, dim3(gl), dim3(256), 0, c->stream, loc, nloc, G, ng, map);
   hipLaunchKernelGGL(k_rl_map, dim3(g), dim3(256), 0, c->stream, ca, cb, n, (const uint32_t*)map);
   return hip_check(c, hipGetLastError(), "relabel_to_global");

@@ -110,10 +110,8 @@ namespace {
 
 // blocks of 256 lanes over n items, each looping.  tab_grid_tab: for the kernels that end in one atomic per block
 // on a shared word -- a few blocks per CU
-unsigned tab_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
-[[maybe_unused]] unsigned tab_grid_tab(uint64_t n) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048));
-}
+unsigned tab_grid(uint64_t n) { return grid_for(n, 256, 16384); }
+[[maybe_unused]] unsigned tab_grid_tab(uint64_t n) { return grid_for(n, 256, 2048); }
 
 // a state's device words meta[0 .. words) -> host_small[8 .. 8 + words), and a wait for the stream
 gs_status tab_read_meta(gs_ctx* c, const unsigned long long* meta, int words) {

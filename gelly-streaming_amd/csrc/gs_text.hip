@@ -6,7 +6,7 @@
 //
 // HBM-bound passes over the bytes, no sort:
 //   k_tx_count   newlines per 16 KiB tile (16-byte loads, one tile per 256-thread block)
-//   k_tx_scan    exclusive scan of the tile counts (one block, coalesced 1024-wide chunks)
+//   k_scan_chunks  exclusive scan of the tile counts (gs_device.hpp: one block, coalesced 1024-wide chunks)
 //   k_tx_starts  record start offsets (u32): tile offset + in-tile rank of each newline
 //   k_tx_parse   256 records per block: their text span staged in LDS with coalesced word loads,
 //                one record per thread: three fields, Java parseLong overflow rules; the first
@@ -58,48 +58,10 @@ __global__ __launch_bounds__(TX_BLOCK) void k_tx_count(const uint8_t* __restrict
   uint32_t c = 0;
 #pragma unroll
   for (int u = 0; u < TX_VEC; ++u) c += __popc(m[u]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-
-// inclusive scan of one value per thread over a 1024-thread block (wave shuffles + 16 wave totals)
-__device__ __forceinline__ uint32_t block_incl_scan1024(uint32_t v, uint32_t* sw, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(v, o, 64);
-    if (lane >= o) v += y;
-  }
-  if (lane == 63) sw[w] = v;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint32_t x = sw[i];
-    before += i < w ? x : 0u;
-    total += x;
-  }
-  __syncthreads();
-  return v + before;
-}
-
-// exclusive scan in place over nt tile counts (coalesced 1024-wide chunks with a carry); total at cnt[nt]
-__global__ __launch_bounds__(1024) void k_tx_scan(uint32_t* __restrict__ cnt, uint32_t nt) {
-  __shared__ uint32_t sw[16];
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nt; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nt ? cnt[i] : 0u;
-    uint32_t total;
-    const uint32_t incl = block_incl_scan1024(v, sw, total);
-    if (i < nt) cnt[i] = carry + incl - v;
-    carry += total;
-  }
-  if (threadIdx.x == 0) cnt[nt] = carry;
 }
 
 // starts[k + 1] = (byte offset of the k-th newline) + 1
@@ -112,26 +74,10 @@ __global__ __launch_bounds__(TX_BLOCK) void k_tx_starts(const uint8_t* __restric
   tile_masks(t, bytes, tile0, m);
   // rank order = byte order: u-major (all threads' u = 0 bytes precede u = 1), so scan per u
   uint32_t k = cnt[blockIdx.x];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int u = 0; u < TX_VEC; ++u) {
-    const uint32_t c = __popc(m[u]);
-    uint32_t v = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(v, o, 64);
-      if (lane >= o) v += y;
-    }
-    if (lane == 63) sw[w] = v;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < TX_BLOCK / 64; ++i) {
-      before += i < w ? sw[i] : 0u;
-      total += sw[i];
-    }
-    __syncthreads();
-    uint32_t r = k + before + v - c;
+    uint32_t total;
+    uint32_t r = k + block_exclusive_sum<TX_BLOCK>((uint32_t)__popc(m[u]), sw, total);
     uint32_t mm = m[u];
     const uint64_t off = tile0 + ((uint64_t)u * TX_BLOCK + threadIdx.x) * 16;
     while (mm) {
@@ -273,7 +219,7 @@ extern "C" gs_status gs_parse_edges_text(gs_ctx* c, const char* text, uint64_t b
   uint32_t* cnt = c->tx_cnt.as<uint32_t>();
   hipLaunchKernelGGL(k_tx_count, dim3(nt), dim3(TX_BLOCK), 0, c->stream, t, bytes, cnt);
   GS_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(1024), 0, c->stream, cnt, nt);
+  hipLaunchKernelGGL(k_scan_chunks<uint32_t>, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, cnt, nt);
   GS_HIP(hipGetLastError());
   uint32_t h[2] = {0, 0};
   uint8_t last = 0;

@@ -103,23 +103,10 @@ __global__ __launch_bounds__(RK_BLOCK) void k_rank_count(const uint32_t* __restr
   if (tid < RK_NC) cnt[tid * tiles + blockIdx.x] = s_c[tid];
 }
 
-// one block: exclusive scan of cnt[0 .. n) (class-major) in place
-__global__ __launch_bounds__(1024) void k_rank_scan(uint32_t* __restrict__ cnt, uint32_t n) {
-  __shared__ uint32_t s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint32_t per = (n + 1023) / 1024, a = min(n, tid * per), b = min(n, a + per);
-  uint32_t sum = 0;
-  for (uint32_t i = a; i < b; ++i) sum += cnt[i];
-  const uint32_t inc = wave_inclusive_sum(sum);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t run = inc - sum;
-  for (int i = 0; i < w; ++i) run += s_w[i];
-  for (uint32_t i = a; i < b; ++i) {
-    const uint32_t x = cnt[i];
-    cnt[i] = run;
-    run += x;
-  }
+// one block: exclusive scan of cnt[0 .. n) in place (the class-major rank counts; the route counts)
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_chunked(uint32_t* __restrict__ cnt, uint32_t n) {
+  __shared__ uint32_t s_w[SCAN_BLOCK / WAVE];
+  block_scan_array_chunked(cnt, n, s_w);
 }
 
 // rank[x] = ids of lower classes + ids of x's class below x (a stable partition: deterministic, so
@@ -138,12 +125,7 @@ __global__ __launch_bounds__(RK_BLOCK) void k_rank_scatter(const uint32_t* __res
   for (int j = 0; j < RK_STEPS; ++j) {
     const uint32_t x = base + j * WAVE + lane;
     const uint32_t c = x < V ? deg_class(deg[x]) : 127u;
-    uint64_t m = ~0ull;
-#pragma unroll
-    for (int bit = 0; bit < 7; ++bit) {
-      const uint64_t bal = __ballot((c >> bit) & 1u);
-      m &= ((c >> bit) & 1u) ? bal : ~bal;
-    }
+    const uint64_t m = match_digit<7>(c, ~0ull);
     cls[j] = c;
     uint32_t b0 = 0;
     if (c < RK_NC) b0 = s_cnt[w][c];
@@ -714,8 +696,7 @@ __global__ __launch_bounds__(UO_BLOCK) void k_tri_uo_count(const uint64_t* __res
       c += head ? 1u : 0u;
       if (hist) wave_hist_add(s_h[w], k[j] & vmask, head, nd);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, WAVE);
+    c = wave_sum(c);
     if (lane == 0) s_w[w] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -975,7 +956,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_count(const uint64_t* __rest
   __syncthreads();
   if (tid < (int)nparts) cnt[(uint64_t)tid * tiles + blockIdx.x] = s_c[tid];
 }
-// (k_rank_scan: the exclusive scan, owner-major) then the scatter; order inside an owner is free
+// (k_scan_chunked: the exclusive scan, owner-major) then the scatter; order inside an owner is free
 // (the owner sorts what it receives)
 __global__ __launch_bounds__(RT_BLOCK) void k_route_scatter(const uint64_t* __restrict__ keys, uint64_t n, uint32_t B,
                                                             uint32_t nparts, RtSplit sp, uint32_t tiles,
@@ -1254,7 +1235,7 @@ gs_status tri_ranks(gs_ctx* c, const TriGeom& g, const uint32_t* deg, uint32_t* 
   GS_TRY(ensure(c, c->tri_tiles, (size_t)rk_tiles * RK_NC * 4 + 8));
   uint32_t* rk_cnt = c->tri_tiles.as<uint32_t>();
   hipLaunchKernelGGL(k_rank_count, dim3(rk_tiles), dim3(RK_BLOCK), 0, c->stream, deg, (uint32_t)g.V, rk_tiles, rk_cnt);
-  hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, c->stream, rk_cnt, rk_tiles * RK_NC);
+  hipLaunchKernelGGL(k_scan_chunked, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, rk_cnt, rk_tiles * RK_NC);
   hipLaunchKernelGGL(k_rank_scatter, dim3(rk_tiles), dim3(RK_BLOCK), 0, c->stream, deg, (uint32_t)g.V, rk_tiles, rk_cnt,
                      rank);
   GS_HIP(hipGetLastError());
@@ -1563,13 +1544,12 @@ gs_status tri_count(gs_ctx* c, uint32_t B, size_t V, uint64_t M, const uint32_t*
   const uint32_t nb_cap = (c->flags & GS_FLAG_TEST_TINY_TABLES) ? 1u : 0xFFFFFFFFu;
   uint32_t* d_nqueue = d_nheavy + 1;
   uint2* queue = c->tri_queue.as<uint2>();
-  hipLaunchKernelGGL(k_tri_lclass, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((V + TH_LCBLOCK - 1) / TH_LCBLOCK,
-                                                                                        4194304 / TH_LCBLOCK))),
+  hipLaunchKernelGGL(k_tri_lclass, dim3(grid_for(V, TH_LCBLOCK, 4194304 / TH_LCBLOCK)),
                      dim3(TH_LCBLOCK), 0, c->stream, nbr, out_range, in_range, (uint32_t)V, 0u, 0xFFFFFFFFu, nb_cap, queue,
                      d_nqueue, c->tri_heavy.as<uint2>(), d_nheavy, d_active, d_merge);
   if (d_active && loops && rank) {
     const uint32_t words = (uint32_t)((V + 31) / 32);
-    hipLaunchKernelGGL(k_tri_loop_only, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, 4096))),
+    hipLaunchKernelGGL(k_tri_loop_only, dim3(grid_for(words, 256, 4096)),
                        dim3(256), 0, c->stream, loops, words, rank, out_range, in_range, d_active);
   }
   hipLaunchKernelGGL(k_tri_light, dim3(8192u), dim3(TH_BLOCK), 0, c->stream, nbr, sfx, out_range, in_range, queue,
@@ -1965,7 +1945,7 @@ gs_status gs_tri_dist_route(gs_ctx* c, const uint32_t* dout, uint32_t nparts, ui
   if (n) {
     hipLaunchKernelGGL(k_route_count, dim3(tiles), dim3(RT_BLOCK), 0, c->stream, c->aux.as<uint64_t>(), n, B, nparts, sp,
                        tiles, cnt);
-    hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, c->stream, cnt, tiles * nparts);
+    hipLaunchKernelGGL(k_scan_chunked, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, cnt, tiles * nparts);
     hipLaunchKernelGGL(k_route_scatter, dim3(tiles), dim3(RT_BLOCK), 0, c->stream, c->aux.as<uint64_t>(), n, B, nparts,
                        sp, tiles, cnt, keys_out);
     GS_HIP(hipGetLastError());
@@ -2041,9 +2021,7 @@ gs_status gs_tri_dist_count(gs_ctx* c, const uint32_t* nbr, uint64_t M, const ui
 }
 
 // ---- boundary adjacency (see k_bd_bounds) -------------------------------------------------------------
-static unsigned bd_grid(uint64_t n, uint64_t per) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, 16384));
-}
+static unsigned bd_grid(uint64_t n, unsigned per) { return grid_for(n, per, 16384); }
 
 gs_status gs_tri_dist_plan(gs_ctx* c, const uint32_t* dplus, uint32_t part, uint32_t nparts, uint64_t* send_elems,
                            uint64_t* recv_elems, uint64_t* M_out) {

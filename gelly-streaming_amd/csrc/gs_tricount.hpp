@@ -466,16 +466,11 @@ __global__ __launch_bounds__(256) void k_tri_hphase_scan(uint32_t* __restrict__ 
   static_assert(TH_PHASES % 256 == 0, "phases per thread");
   constexpr uint32_t PT = TH_PHASES / 256;
   __shared__ uint32_t s_w[256 / WAVE];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  uint32_t v[PT], x = 0;
+  const int tid = threadIdx.x;
+  uint32_t v[PT], x = 0, total;
 #pragma unroll
   for (uint32_t j = 0; j < PT; ++j) x += (v[j] = hist[tid * PT + j]);
-  const uint32_t inc = wave_inclusive_sum(x);
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t off = 0;
-  for (int i = 0; i < w; ++i) off += s_w[i];
-  off += inc - x;
+  uint32_t off = block_exclusive_sum<256>(x, s_w, total);
 #pragma unroll
   for (uint32_t j = 0; j < PT; ++j) {
     hist[tid * PT + j] = off;

@@ -369,7 +369,7 @@ namespace {
 enum { TSB_CNT, TSB_OFF, TSB_ROWS, TSB_INFO, TSB_IDS, TSB_FM, TSB_NEXT, TSB_SLOTS, TSB_FILTER, TSB_EVK, TSB_WORK };
 static_assert(TSB_WORK < 12, "gs_ctx::ts");
 
-unsigned ts_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384)); }
+unsigned ts_grid(uint64_t n) { return grid_for(n, 256, 16384); }
 
 gs_status check_state(gs_ctx* c, const gs_trisample* t) {
   if (!c) return GS_EINVAL;
@@ -528,7 +528,7 @@ gs_status gs_trisample_edges(gs_ctx* c, gs_trisample* t, const gs_edge_batch* b,
     GS_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device));
     c->n_cu = std::max(1, cu);
   }
-  const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, 2ull * c->n_cu));
+  const unsigned sgrid = grid_for(tiles, 1, 2 * c->n_cu);
   if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0)
     hipLaunchKernelGGL(k_ts_stream<true>, dim3(sgrid), dim3(256), 0, c->stream, tb, n, ep, tab, use_filter);
   else

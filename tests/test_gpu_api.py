@@ -152,6 +152,28 @@ def test_triangles_matches_reference_rule(engine, oracle):
         assert (ex, wrapped, has_g) == (ex_ref, w_ref, has_ref), trial
 
 
+@pytest.mark.parametrize("bits", [16, 17, 18])
+def test_triangles_rank_scan_shapes(engine, oracle, bits):
+    """The degree-class rank counts are scanned by one block, a contiguous chunk per thread, over
+    (V / 8192) tiles x 64 classes, V the id range rounded up to a power of two: 2^16 ids give 512 counts (one
+    per thread, half the block idle), 2^17 give 1024 (one per thread, every thread busy), 2^18 give 2048 (two
+    per thread).  Triangles on random ids over the whole range, a hub for the upper degree classes, and a path
+    through the highest id, so that a count placed wrongly in any tile misranks vertices of some triangle."""
+    V = 1 << bits
+    rng = np.random.default_rng(bits)
+    t = rng.integers(0, V, (1500, 3)).astype(np.int64)
+    t = t[(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 0] != t[:, 2])]
+    hub = rng.choice(V - 1, 300, replace=False).astype(np.int64)
+    s = np.concatenate([t[:, 0], t[:, 1], t[:, 2], np.full(300, V - 1), hub[:-1], [V - 1, V - 2]])
+    d = np.concatenate([t[:, 1], t[:, 2], t[:, 0], hub, hub[1:], [V - 2, V - 3]])
+    p = rng.permutation(len(s))
+    s, d = s[p], d[p]
+    assert s.min() >= 0 and max(s.max(), d.max()) == V - 1 and (s != d).all()
+    w_fwd, ex_fwd, has = oracle.window_triangles_fwd(s, d)
+    assert ex_fwd >= len(t) and has
+    assert engine.triangles(s, d) == (ex_fwd, w_fwd, has)
+
+
 def test_triangles_empty_window(engine):
     ex, wrapped, has = engine.triangles(np.empty(0, np.int64), np.empty(0, np.int64))
     assert (ex, wrapped, has) == (0, 0, False)
@@ -352,6 +374,18 @@ def test_candidate_count_sizing(engine, oracle, kind):
     for _ in range(3):
         s, d = _cand_case(oracle, rng, kind)
         assert engine.candidate_count(s, d) == oracle.candidate_count(s, d)
+
+
+def test_candidate_count_scan_carry(engine, oracle):
+    """2,100,000 disjoint edges: 4,200,000 vertices and as many neighbour records, more than the 1024 tiles of
+    4096 elements that one trip of the u64 scan's top level covers, so its carry crosses into a second trip.
+    Every vertex has one neighbour: its neighbour record and nothing else."""
+    n = 2_100_000
+    p = np.random.default_rng(41).permutation(2 * n).astype(np.int64)
+    s, d = p[:n], p[n:]
+    want = oracle.candidate_count(s, d)
+    assert want == 2 * n
+    assert engine.candidate_count(s, d) == want
 
 
 def test_text_to_window_reduce(engine, oracle):

@@ -385,3 +385,32 @@ def test_split_window_s22_eight_ranks(pkg, oracle):
     res, errs = run_group(pkg, P, fn_fold, timeout=600)
     assert not errs, errs
     check_union(res, oracle.window_fold_degree_max_mt(fs, fd, 1, -5), P)
+
+
+def test_reduce_dist_owner_scan_chunks(pkg, oracle):
+    """The owner partition of a rank whose local window took the sort path scans tiles x P counts (tiles of
+    2048 partials) with one 1024-thread block, a contiguous chunk per thread.  At P = 8 the ranks here hold
+    127, 128, 129 and 280 tiles of distinct sources: 1016 counts (one per thread, the last threads idle), 1024
+    (one per thread, every thread busy), 1032 (two per thread, threads from 516 up idle) and 2240 (three per
+    thread, the last chunk ragged); the others a few thousand, one and none.  Ids 1021 apart keep every large
+    rank's vertex range past the bucket path's (stage_times().path == 0: the sort path)."""
+    P = 8
+    U = (280 * 2048 - 5, 129 * 2048 - 100, 128 * 2048, 127 * 2048 - 1, 5000, 1, 0, 3000)
+    start = (0, 400_000, 100_000, 650_000, 10, 123_456, 0, 700_000)   # overlapping id ranges: owners merge
+    G = max(a + u for a, u in zip(start, U))
+    rng = np.random.default_rng(0x5EED13)
+    ids = np.arange(G, dtype=np.int64) * 1021 + 7
+    src = [ids[a:a + u][rng.permutation(u)] for a, u in zip(start, U)]
+    dst = [rng.integers(0, 1 << 40, u).astype(np.int64) for u in U]
+    val = [rng.integers(-1 << 40, 1 << 40, u).astype(np.int64) for u in U]
+
+    def fn(r, e):
+        out = e.reduce_dist(src[r], dst[r], val[r], 1, 0)
+        return out, e.stage_times().path
+
+    res, errs = run_group(pkg, P, fn)
+    assert not errs, errs
+    for r in range(4):
+        assert res[r][1] == 0, (r, res[r][1])
+    s, d, v = (np.concatenate(x) for x in (src, dst, val))
+    check_union([res[r][0] for r in range(P)], oracle.window_reduce(s, d, v, 1, 0), P)

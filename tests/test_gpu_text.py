@@ -1,5 +1,5 @@
 """GPU: gs_parse_edges_text (csrc/gs_text.hip) on the paths tests/test_gpu_api.py never reaches: the
-unstaged half of k_tx_parse and its 4096-word threshold, k_tx_scan's carry, tiles without a newline,
+unstaged half of k_tx_parse and its 4096-word threshold, k_scan_chunks' carry, tiles without a newline,
 unaligned device text, bytes past the end, several malformed records, the capacity protocol.
 
 Expected values come from tests/textparse_ref.py (an independent restatement of the Java rules); the

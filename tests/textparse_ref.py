@@ -68,7 +68,7 @@ def parse(text: bytes):
 # ---- launch geometry of gelly-streaming_amd/csrc/gs_text.hip ------------------------------------------
 # TX_TILE = TX_BLOCK * 16 * TX_VEC = 16384 bytes per k_tx_count / k_tx_starts block;
 # TX_BLOCK = 256 records per k_tx_parse block; TX_LDS_WORDS = 4096 words of record text a parse block
-# can stage (staged = w1 - w0 <= TX_LDS_WORDS); k_tx_scan walks the tile counts in 1024-wide chunks.
+# can stage (staged = w1 - w0 <= TX_LDS_WORDS); k_scan_chunks walks the tile counts in 1024-wide chunks.
 TILE = 16384
 BLOCK_RECORDS = 256
 LDS_WORDS = 4096
@@ -78,7 +78,7 @@ SCAN_CHUNK = 1024
 class Plan(NamedTuple):
     tiles: int                  # k_tx_count / k_tx_starts grid
     tile_newlines: np.ndarray   # newlines of each tile
-    scan_chunks: int            # trips of k_tx_scan's loop (a carry crosses when > 1)
+    scan_chunks: int            # trips of k_scan_chunks' loop (a carry crosses when > 1)
     records: int
     starts: np.ndarray          # byte offset of each record (and of the end after the last newline)
     block_words: np.ndarray     # per parse block, w1 - w0
