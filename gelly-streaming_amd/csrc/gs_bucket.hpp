@@ -59,8 +59,19 @@ template <class P>
 __host__ __device__ constexpr uint32_t bk_inline_k() {
   return std::is_integral_v<typename P::A> && GS_BK_INLINE_K > 1 ? (uint32_t)GS_BK_INLINE_K : 0u;
 }
+// Cache hints of the read-once streams (ld_stream, gs_device.hpp; DESIGN.md §4 "Stream loads"): the speculative
+// scatters' key / value columns, and the partition k_bk_accum reads back -- but for 8-byte values in the unpacked
+// path (Double sums), whose scatter and accumulate measured no faster or slower with them.  Stores, cursor atomics, the escape
+// re-read, slabs and staging keep the default policy.
+#ifndef GS_NT_COLUMNS
+#define GS_NT_COLUMNS 1
+#endif
+#ifndef GS_NT_PARTITION
+#define GS_NT_PARTITION 1
+#endif
+constexpr bool NT_COLUMNS = GS_NT_COLUMNS != 0, NT_PARTITION = GS_NT_PARTITION != 0;
 #ifndef GS_BK_S8
-#define GS_BK_S8 14   // 2^S vertices per bucket with 8-byte accumulators (BkVal)
+#define GS_BK_S8 14  // 2^S vertices per bucket with 8-byte accumulators (BkVal)
 #endif
 constexpr int BK_ACC_BLOCK = GS_BK_ACC_BLOCK;     // 16 waves: one workgroup per CU (LDS-bound)
 constexpr int BK_NW = BK_ACC_BLOCK / WAVE;
@@ -1353,15 +1364,15 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
 #pragma unroll
     for (int u = 0; u < ITEMS; u += 2) {
       const uint32_t r = r0 + 2u * ((uint32_t)(u >> 1) * BLOCK + tid);
-      const ulonglong2 k2 = *reinterpret_cast<const ulonglong2*>(kcol + r);
+      const u64x2 k2 = ld16<NT_COLUMNS>(kcol + r);
       kk[u] = (int64_t)k2.x;
       kk[u + 1] = (int64_t)k2.y;
       if constexpr (sizeof(V) == 8) {
-        const ulonglong2 v2 = *reinterpret_cast<const ulonglong2*>(es.val + r);
+        const u64x2 v2 = ld16<NT_COLUMNS>(es.val + r);
         vv[u] = (V)v2.x;
         vv[u + 1] = (V)v2.y;
       } else {
-        const uint2 v2 = *reinterpret_cast<const uint2*>(es.val + r);
+        const u32x2 v2 = ld8w<NT_COLUMNS>(es.val + r);
         vv[u] = (V)v2.x;
         vv[u + 1] = (V)v2.y;
       }
@@ -1376,8 +1387,8 @@ void k_sp_scatter_pack(BaseSrc<V, DIR, PAY_VAL> es, uint64_t n, int S, uint32_t 
         i = r >> 1;
         rev = r & 1u;
       }
-      kk[u] = (rev ? es.dst : es.src)[i];
-      vv[u] = es.val[i];
+      kk[u] = (int64_t)ld8<NT_COLUMNS>((rev ? es.dst : es.src) + i);
+      vv[u] = ld_stream<NT_COLUMNS>(es.val + i);
     }
   }
   for (uint32_t i = tid; i < nbp; i += BLOCK) s_cnt[i] = 0;
@@ -1534,6 +1545,10 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
   // full OUT / IN tiles of 16-byte aligned columns: two records per lane and load, as k_sp_scatter_pack
   // (record u of a thread is jof(u) of the tile, which only the dead-lane check uses)
   static_assert(ITEMS % 2 == 0, "two records per lane and load");
+  // 8-byte values keep the default cache policy on the columns: with the hint Double C2's scatter gained 0 - 0.04 ms
+  // and its accumulate lost 0.03 - 0.04 ms, box by box; keys + neighbours (the folds) and 4-byte values
+  // take the hint
+  constexpr bool NT = NT_COLUMNS && !(PAY == PAY_VAL && sizeof(V) == 8);
   const int64_t* kcol = DIR == DIR_IN ? es.dst : es.src;
   const void* pcol = PAY == PAY_VAL ? (const void*)es.val : PAY == PAY_NBR ? (const void*)(DIR == DIR_IN ? es.src : es.dst)
                                                                           : (const void*)kcol;
@@ -1545,21 +1560,21 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 #pragma unroll
     for (int u = 0; u < ITEMS; u += 2) {
       const uint32_t r = r0 + 2u * ((uint32_t)(u >> 1) * BLOCK + tid);
-      const ulonglong2 k2 = *reinterpret_cast<const ulonglong2*>(kcol + r);
+      const u64x2 k2 = ld16<NT>(kcol + r);
       kk[u] = (int64_t)k2.x;
       kk[u + 1] = (int64_t)k2.y;
       if constexpr (PAY == PAY_NBR) {
-        const ulonglong2 v2 = *reinterpret_cast<const ulonglong2*>((const int64_t*)pcol + r);
+        const u64x2 v2 = ld16<NT>((const int64_t*)pcol + r);
         vv[u] = (V)v2.x;
         vv[u + 1] = (V)v2.y;
       } else if constexpr (PAY == PAY_VAL && sizeof(V) == 8) {
-        const ulonglong2 v2 = *reinterpret_cast<const ulonglong2*>(es.val + r);
-        vv[u] = __builtin_bit_cast(V, v2.x);
-        vv[u + 1] = __builtin_bit_cast(V, v2.y);
+        const u64x2 v2 = ld16<NT>(es.val + r);
+        vv[u] = __builtin_bit_cast(V, (unsigned long long)v2.x);
+        vv[u + 1] = __builtin_bit_cast(V, (unsigned long long)v2.y);
       } else if constexpr (PAY == PAY_VAL && sizeof(V) == 4) {
-        const uint2 v2 = *reinterpret_cast<const uint2*>(es.val + r);
-        vv[u] = __builtin_bit_cast(V, v2.x);
-        vv[u + 1] = __builtin_bit_cast(V, v2.y);
+        const u32x2 v2 = ld8w<NT>(es.val + r);
+        vv[u] = __builtin_bit_cast(V, (uint32_t)v2.x);
+        vv[u + 1] = __builtin_bit_cast(V, (uint32_t)v2.y);
       }
     }
   } else {
@@ -1572,9 +1587,9 @@ __global__ __launch_bounds__(SPU_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
         i = r >> 1;
         rev = r & 1u;
       }
-      kk[u] = (rev ? es.dst : es.src)[i];
-      if constexpr (PAY == PAY_VAL) vv[u] = es.val[i];
-      else if constexpr (PAY == PAY_NBR) vv[u] = (V)(rev ? es.src : es.dst)[i];
+      kk[u] = (int64_t)ld8<NT>((rev ? es.dst : es.src) + i);
+      if constexpr (PAY == PAY_VAL) vv[u] = ld_stream<NT>(es.val + i);
+      else if constexpr (PAY == PAY_NBR) vv[u] = (V)(int64_t)ld8<NT>((rev ? es.src : es.dst) + i);
     }
   }
   uint32_t ovf = 0, kb[ITEMS];
@@ -1857,7 +1872,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
         hh = px < SP_NSEG && (j < 3 ? q < xa0 : q < xp1);
         if (hh) {
           hq = q;
-          hx = src.rec[q];
+          hx = ld_stream<NT_PARTITION>(src.rec + q);
         }
       }
     }
@@ -1871,7 +1886,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
   __syncthreads();
   constexpr int U4 = UNROLL / 2 > 0 ? UNROLL / 2 : 1;
   // (GS_BK_PREFETCH) the next item's first group of 16-byte loads, issued before this item's finalize
-  uint4 xp[U4];
+  u32x4 xp[U4];
   uint32_t qp[U4];
   bool pf = false;
   for (int sl = 0;; sl ^= 1) {
@@ -1890,7 +1905,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
       // n4 groups of 4 records, group g at uint4 index q4_of(g) of the partition
       auto stream = [&](uint32_t n4, auto q4_of) {
         for (uint32_t g4 = tid; g4 < n4; g4 += STEP) {
-          uint4 x[U4];
+          u32x4 x[U4];
           uint32_t qi[U4];
           if (pf) {   // the first group, loaded before the previous item's finalize
 #pragma unroll
@@ -1904,7 +1919,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
             for (int u = 0; u < U4; ++u) {   // unconditional, clamped: see k_dp_hist
               const uint32_t g = g4 + (uint32_t)u * BK_ACC_BLOCK;
               qi[u] = q4_of(g < n4 ? g : n4 - 1);
-              x[u] = rec4[qi[u]];
+              x[u] = ld16w<NT_PARTITION>(rec4 + qi[u]);
             }
           }
           // every load of the group issued before the first use (the scheduler moved the first
@@ -1941,8 +1956,8 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
       if (!seg_cur) {   // records [r0, r1) of the partition
         const uint32_t r0 = b0 + m.begin, r1 = b0 + m.end;
         const uint32_t a0 = min(r1, (r0 + 3) & ~3u), a1 = max(a0, r1 & ~3u);
-        if (r0 + tid < a0) add1(src, r0 + tid, src.rec[r0 + tid]);
-        if (a1 + tid < r1) add1(src, a1 + tid, src.rec[a1 + tid]);
+        if (r0 + tid < a0) add1(src, r0 + tid, ld_stream<NT_PARTITION>(src.rec + r0 + tid));
+        if (a1 + tid < r1) add1(src, a1 + tid, ld_stream<NT_PARTITION>(src.rec + a1 + tid));
         stream((a1 - a0) / 4, [&](uint32_t g) { return a0 / 4 + g; });
       } else {
         if (hh) add1(src, hq, hx);   // wave 0's staged head / tail records
@@ -1973,6 +1988,9 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
       // ran at 4.3 TB/s.)
       using V = std::remove_cv_t<std::remove_pointer_t<decltype(src.vals)>>;
       constexpr bool HV = !std::is_same_v<V, uint8_t>;
+      // 8-byte payloads read the partition with the default policy: the hint cost Double C2's accumulate 0.075 ms
+      // (0.541 -> 0.616 ms, a 2.68 GB partition), with or without the hint on the columns
+      constexpr bool NT = NT_PARTITION && sizeof(V) != 8;
       auto add1 = [&](uint32_t q) {
         uint32_t k;
         V v{};
@@ -1986,25 +2004,27 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
       const uint32_t q_end = a1 / 4;
       const uint2* k4 = reinterpret_cast<const uint2*>(src.keys);
       for (uint32_t q4 = a0 / 4 + tid; q4 < q_end; q4 += STEP) {
-        uint2 kx[U4];
+        u32x2 kx[U4];
         V vx[U4][4];
 #pragma unroll
         for (int u = 0; u < U4; ++u) {   // unconditional, clamped (see k_dp_hist)
           const uint32_t qq = min(q4 + (uint32_t)u * BK_ACC_BLOCK, q_end - 1);
-          kx[u] = k4[qq];
+          kx[u] = ld8w<NT>(k4 + qq);
+          // (the casts make each component a value first: __builtin_bit_cast of the component expression itself
+          // read the vector's first element for every component)
           if constexpr (HV && sizeof(V) == 4) {
-            const uint4 w = reinterpret_cast<const uint4*>(src.vals)[qq];
-            vx[u][0] = __builtin_bit_cast(V, w.x);
-            vx[u][1] = __builtin_bit_cast(V, w.y);
-            vx[u][2] = __builtin_bit_cast(V, w.z);
-            vx[u][3] = __builtin_bit_cast(V, w.w);
+            const u32x4 w = ld16w<NT>(reinterpret_cast<const uint4*>(src.vals) + qq);
+            vx[u][0] = __builtin_bit_cast(V, (uint32_t)w.x);
+            vx[u][1] = __builtin_bit_cast(V, (uint32_t)w.y);
+            vx[u][2] = __builtin_bit_cast(V, (uint32_t)w.z);
+            vx[u][3] = __builtin_bit_cast(V, (uint32_t)w.w);
           } else if constexpr (HV && sizeof(V) == 8) {
-            const ulonglong2 w0 = reinterpret_cast<const ulonglong2*>(src.vals)[2 * qq];
-            const ulonglong2 w1 = reinterpret_cast<const ulonglong2*>(src.vals)[2 * qq + 1];
-            vx[u][0] = __builtin_bit_cast(V, w0.x);
-            vx[u][1] = __builtin_bit_cast(V, w0.y);
-            vx[u][2] = __builtin_bit_cast(V, w1.x);
-            vx[u][3] = __builtin_bit_cast(V, w1.y);
+            const u64x2 w0 = ld16<NT>(reinterpret_cast<const ulonglong2*>(src.vals) + 2 * qq);
+            const u64x2 w1 = ld16<NT>(reinterpret_cast<const ulonglong2*>(src.vals) + 2 * qq + 1);
+            vx[u][0] = __builtin_bit_cast(V, (unsigned long long)w0.x);
+            vx[u][1] = __builtin_bit_cast(V, (unsigned long long)w0.y);
+            vx[u][2] = __builtin_bit_cast(V, (unsigned long long)w1.x);
+            vx[u][3] = __builtin_bit_cast(V, (unsigned long long)w1.y);
           } else {
             vx[u][0] = vx[u][1] = vx[u][2] = vx[u][3] = V{};
           }
@@ -2072,7 +2092,7 @@ __global__ __launch_bounds__(BK_ACC_BLOCK) void k_bk_accum(Src src, const BkItem
 #pragma unroll
           for (uint32_t x = 1; x < SP_NSEG; ++x) b += g >= pre[x] ? dq[x] : 0u;
           qp[u] = g + b;
-          xp[u] = rec4[qp[u]];
+          xp[u] = ld16w<NT_PARTITION>(rec4 + qp[u]);
         }
         pf = true;
       }

@@ -63,6 +63,30 @@ __device__ __forceinline__ T wave_sum(T x) {
   return x;
 }
 
+// ---- streaming global loads ----------------------------------------------------------------------------------
+// One load instruction per call, NT chosen at compile time: plain (the default cache policy) or non-temporal (`nt`:
+// a stream that is read once).  The 16- and 8-byte forms are clang ext-vector types: a load through one stays one
+// global_load_dwordx4 / dwordx2, where HIP's ulonglong2 / uint2 (structs of scalars) are split into their members
+// and may be merged again differently -- a branch of 16-byte loads next to a branch of 8-byte loads compiled to one
+// shared tail of 8-byte loads that way.  The address is aligned to the size of T.
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+template <bool NT, typename T>
+__device__ __forceinline__ T ld_stream(const T* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT>
+__device__ __forceinline__ u64x2 ld16(const void* p) { return ld_stream<NT>(static_cast<const u64x2*>(p)); }
+template <bool NT>
+__device__ __forceinline__ u32x4 ld16w(const void* p) { return ld_stream<NT>(static_cast<const u32x4*>(p)); }
+template <bool NT>
+__device__ __forceinline__ u32x2 ld8w(const void* p) { return ld_stream<NT>(static_cast<const u32x2*>(p)); }
+template <bool NT>
+__device__ __forceinline__ uint64_t ld8(const void* p) { return ld_stream<NT>(static_cast<const uint64_t*>(p)); }
+
 // The block-wide exclusive scan of one value per thread: returns the sum of x over the threads below this one
 // and sets `total` to the sum over the whole block, in every thread (an inclusive result is the return value + x).
 //  - BLOCK is the launch's thread count (one-dimensional): exactly BLOCK / WAVE wave totals are written and read,
