@@ -162,8 +162,14 @@ inline gs_status deliver(gs_ctx* c, void* dst, const void* staged, size_t bytes,
   return GS_OK;
 }
 
+// Every entry point that takes an edge batch validates it here first, before begin_call: a call refused for its
+// arguments is still "another entry point called on the ctx", so it ends a chunked-candidates session like one
+// that ran (gs_candidates_begin sets cand_seq after its own check)
+inline void end_candidates_session(gs_ctx* c) { c->cand_seq = ~0ull; }
+
 inline gs_status check_batch(gs_ctx* c, const gs_edge_batch* b, int dir) {
   if (!c) return GS_EINVAL;
+  end_candidates_session(c);
   if (!b) return set_error(c, GS_EINVAL, "null batch");
   if (dir < 0 || dir > 2) return set_error(c, GS_EINVAL, "bad EdgeDirection %d", dir);
   if (b->n && (!b->src || !b->dst)) return set_error(c, GS_EINVAL, "null src/dst");
@@ -177,6 +183,7 @@ inline gs_status check_batch(gs_ctx* c, const gs_edge_batch* b, int dir) {
 // reduce / fold / degree fold: any window size (chunked above one pass's record cap, gs_engine.hip)
 inline gs_status check_batch_any(gs_ctx* c, const gs_edge_batch* b, int dir) {
   if (!c) return GS_EINVAL;
+  end_candidates_session(c);
   if (!b) return set_error(c, GS_EINVAL, "null batch");
   if (dir < 0 || dir > 2) return set_error(c, GS_EINVAL, "bad EdgeDirection %d", dir);
   if (b->n && (!b->src || !b->dst)) return set_error(c, GS_EINVAL, "null src/dst");
