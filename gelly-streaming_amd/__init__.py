@@ -16,8 +16,8 @@ from .engine import (AssignComponentsState, CommGroup, ContinuousState, Distinct
 from .functions import (Collector, CountFold, CountReduce, DegreeMaxNeighborFold, EdgesApply, EdgesFold,  # noqa: F401
                         EdgesReduce, MaxReduce, MaxValuesFold, MinReduce, MinValuesFold, SumReduce, SumValuesFold)
 from .stream import (AscendingTimestampExtractor, DataStream, EdgeColumns, EdgeDirection,  # noqa: F401
-                     EdgeValueTimestampExtractor, GraphWindowStream, SimpleEdgeStream, StreamExecutionEnvironment,
-                     Time, TimeUnit)
+                     EdgeValueTimestampExtractor, GraphWindowStream, SimpleEdgeStream, SlicePlan,
+                     StreamExecutionEnvironment, Time, TimeUnit, plan_slice, window_span)
 from .triangles import CountTriangles, GenerateCandidateEdges, window_triangles  # noqa: F401
 from .triangle_estimate import (TriangleSummer, broadcast_triangle_count,  # noqa: F401
                                 incidence_sampling_triangle_count)

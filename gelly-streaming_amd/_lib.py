@@ -62,7 +62,8 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_match_create", "gs_match_destroy", "gs_match_edges", "gs_match_size", "gs_match_capacity",
            "gs_match_last_batch", "gs_match_export", "gs_match_import",
            "gs_assign_create", "gs_assign_destroy", "gs_assign_edges", "gs_assign_size", "gs_assign_capacity",
-           "gs_assign_last_batch", "gs_assign_export", "gs_assign_import")
+           "gs_assign_last_batch", "gs_assign_export", "gs_assign_import",
+           "gs_slice_reduce", "gs_slice_fold_degree_max")
 
 P = ctypes.c_void_p
 u64, i64, i32, u32 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
@@ -115,6 +116,12 @@ class GsTrisampleHeader(ctypes.Structure):   # gs_trisample_header: a sampler ch
 class GsDegreeOut(ctypes.Structure):
     _fields_ = [("keys", P), ("degree", P), ("max_neighbor", P), ("capacity", u64),
                 ("n_out", ctypes.POINTER(u64)), ("mem", i32), ("reserved", i32)]
+
+
+class GsSlicedOut(ctypes.Structure):   # gs_sliced_out: every window of a batch (gs_slice_reduce)
+    _fields_ = [("window_start", P), ("row_begin", P), ("keys", P), ("vals", P), ("vals2", P),
+                ("capacity_windows", u64), ("capacity_rows", u64), ("n_windows", ctypes.POINTER(u64)),
+                ("n_rows", ctypes.POINTER(u64)), ("mem", i32), ("reserved", i32)]
 
 
 class GsCsrOut(ctypes.Structure):
@@ -219,6 +226,9 @@ def load() -> ctypes.CDLL:
         "gs_window_reduce": (st, [P, ctypes.POINTER(GsEdgeBatch), i32, i32, ctypes.POINTER(GsVertexOut)]),
         "gs_window_fold": (st, [P, ctypes.POINTER(GsEdgeBatch), i32, i32, P, ctypes.POINTER(GsVertexOut)]),
         "gs_window_fold_degree_max": (st, [P, ctypes.POINTER(GsEdgeBatch), i32, i64, ctypes.POINTER(GsDegreeOut)]),
+        "gs_slice_reduce": (st, [P, ctypes.POINTER(GsEdgeBatch), P, i32, i64, i32, i32, P, ctypes.POINTER(GsSlicedOut)]),
+        "gs_slice_fold_degree_max": (st, [P, ctypes.POINTER(GsEdgeBatch), P, i32, i64, i32, i64,
+                                          ctypes.POINTER(GsSlicedOut)]),
         "gs_window_csr": (st, [P, ctypes.POINTER(GsEdgeBatch), i32, ctypes.POINTER(GsCsrOut)]),
         "gs_window_candidates": (st, [P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsPairOut)]),
         "gs_window_candidates_part": (st, [P, ctypes.POINTER(GsEdgeBatch), u32, u32, ctypes.POINTER(GsPairOut)]),

@@ -63,6 +63,26 @@ __device__ __forceinline__ T wave_sum(T x) {
   return x;
 }
 
+// the wave's minimum / maximum, in every lane (T of 4 or 8 bytes)
+template <typename T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T y = __shfl_xor(x, o, WAVE);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T y = __shfl_xor(x, o, WAVE);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+
 // ---- streaming global loads ----------------------------------------------------------------------------------
 // One load instruction per call, NT chosen at compile time: plain (the default cache policy) or non-temporal (`nt`:
 // a stream that is read once).  The 16- and 8-byte forms are clang ext-vector types: a load through one stays one

@@ -468,6 +468,8 @@ void gs_destroy(gs_ctx* c) {
     if (b.p) hipFree(b.p);
   for (DevBuf& b : c->ts)
     if (b.p) hipFree(b.p);
+  for (DevBuf& b : c->sl)
+    if (b.p) hipFree(b.p);
   for (DevBuf& b : c->tri_bd)
     if (b.p) hipFree(b.p);
   for (DevBuf& b : c->tri_rl)

@@ -116,7 +116,9 @@ struct gs_ctx {
   gs::DevBuf ts[12];             // sampling triangle estimators (gs_trisample.hip): epochs, wanted table, events;
                                  // gs_matching.hip: per-edge slots, pending lists, footprints, event scratch
                                  // gs_assign.hip: per-edge slots, roots, live lists, losers; record scratch; [11] growth map
-  uint32_t tri_guess_B = 0;      // triangles: the previous window's id width (its partition histograms ride the id scan)
+  gs::DevBuf sl[6];              // all windows of a batch (gs_slice.hip): staged timestamps, composite keys, payloads,
+                                 // the rows' window indices, tile counts + range words, staged window columns
+  uint32_t tri_guess_B = 0;     // triangles: the previous window's id width (its partition histograms ride the id scan)
   uint32_t tri_B = 0;            // split-window triangles: id geometry of the current window
   uint64_t tri_key_xor = 0;
   // split-window triangles, boundary adjacency (gs_tri_dist_plan / _need / _serve / _assemble): this

@@ -330,6 +330,62 @@ class Engine:
         U = n_out.value
         return keys[:U], deg[:U], mx[:U]
 
+    # -- every tumbling window of a batch in one call (gs_slice_reduce) -----------------------------
+    def _sliced(self, call, b, dev, ts, window_ms, direction, ob_dtype, degree: bool, windows_hint=None):
+        """Rows are sized at R; windows by a first guess (windows_hint, an upper bound the caller knows, or
+        2^16), with one retry at the count GS_ECAPACITY reports."""
+        if _is_torch(ts):
+            assert ts.is_cuda and ts.is_contiguous() and ts.dtype == _out_dtypes()[np.int64], "ts: int64, contiguous"
+            ts_mem = L.GS_MEM_DEVICE
+        else:
+            ts = np.ascontiguousarray(ts, dtype=np.int64)
+            ts_mem = L.GS_MEM_HOST
+        if len(ts) != b.n:
+            raise ValueError("ts must have one timestamp per edge")
+        R = self._records(b.n, direction)
+        keys = self._empty(dev, R, np.int64)
+        vals = self._empty(dev, R, ob_dtype)
+        vals2 = self._empty(dev, R, np.int64) if degree else None
+        nw, nr = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        cap_w = min(R, int(windows_hint) if windows_hint else 1 << 16)
+        for attempt in (0, 1):
+            ws = self._empty(dev, cap_w, np.int64)
+            rb = self._empty(dev, cap_w + 1, np.uint64)
+            out = L.GsSlicedOut(_ptr(ws), _ptr(rb), _ptr(keys), _ptr(vals), _ptr(vals2), cap_w, R, ctypes.pointer(nw),
+                                ctypes.pointer(nr), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+            st = call(ctypes.byref(b), _ptr(ts), ts_mem, int(window_ms), int(direction), ctypes.byref(out))
+            if st == L.GS_ECAPACITY and attempt == 0 and nr.value <= R:
+                cap_w = nw.value
+                continue
+            self._check(st)
+            break
+        W, U = nw.value, nr.value
+        rows = (keys[:U], vals[:U]) + ((vals2[:U],) if degree else ())
+        return (ws[:W], rb[:W + 1]) + rows
+
+    def slice_reduce(self, src, dst, val, ts, window_ms, direction, op, init=None, windows_hint=None):
+        """gs_slice_reduce: reduceOnEdges (init None) or foldNeighbors(init, op) of every tumbling window of the
+        batch at once.  Returns (window_start[W], row_begin[W + 1], keys[U], values[U]): window w owns rows
+        row_begin[w] .. row_begin[w + 1], the rows of the per-window call in window order.  ts: numpy or a device
+        tensor, any order.  GsError GS_EUNSUPPORTED when the (window, vertex) key does not fit 64 bits."""
+        b, keep, dev = self._batch(src, dst, None if op == L.GS_OP_COUNT else val)
+        odt = np.int64 if op == L.GS_OP_COUNT else L.NP_DTYPE[b.val_dtype]
+        ia = None if init is None else np.array([init], dtype=odt)
+
+        def call(bp, tp, ts_mem, size, d, op_out):
+            return self._L.gs_slice_reduce(self.ctx, bp, tp, ts_mem, size, d, int(op),
+                                           None if ia is None else ia.ctypes.data_as(ctypes.c_void_p), op_out)
+        return self._sliced(call, b, dev, ts, window_ms, direction, odt, False, windows_hint)
+
+    def slice_fold_degree_max(self, src, dst, ts, window_ms, direction, init_max: int = -(1 << 63),
+                              windows_hint=None):
+        """gs_slice_fold_degree_max: (window_start, row_begin, keys, degree, max_neighbor), as slice_reduce."""
+        b, keep, dev = self._batch(src, dst, None)
+
+        def call(bp, tp, ts_mem, size, d, op_out):
+            return self._L.gs_slice_fold_degree_max(self.ctx, bp, tp, ts_mem, size, d, int(init_max), op_out)
+        return self._sliced(call, b, dev, ts, window_ms, direction, np.int64, True, windows_hint)
+
     def csr(self, src, dst, val, direction):
         """gs_window_csr: (keys, offsets[U+1], neighbours[R], values[R] or None), arrival order per vertex."""
         b, keep, dev = self._batch(src, dst, val)

@@ -23,7 +23,7 @@ from enum import IntEnum
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, _is_torch
+from .engine import Engine, GsError, _gs_dtype, _is_torch
 from .functions import (Collector, EdgesApply, EdgesFold, EdgesReduce, DegreeMaxNeighborFold, _BuiltinFold,
                         _BuiltinReduce)
 
@@ -75,6 +75,62 @@ class EdgeColumns:
         return len(self.src)
 
 
+# ---- slice(): one engine call per window, or one for all of them (gs_slice_reduce) -----------------------
+# Mean (direction-expanded) records per window below which "auto" takes the one batched call: the largest measured
+# mean at which every batched repetition beat every repetition of the per-window loop on an MI355X, 2^20 records
+# (I64 SUM OUT; the degree fold ALL still won at 2^21), halved because boxes differ by about 5 %
+# (profiles/slice_batched/README.md).  At 2^22 records per window the loop won every repetition.
+SLICE_CROSSOVER = 1 << 19
+SLICE_MAX_RECORDS = (1 << 32) - 1   # direction-expanded records of one batched call (check_batch)
+
+
+@dataclass(frozen=True)
+class SlicePlan:
+    """What plan_slice decided: batched (one gs_slice_* call) or the per-window loop, and why."""
+    batched: bool
+    reason: str
+    windows: int = 0          # windows the timestamps span (an upper bound on the non-empty ones)
+
+
+def window_span(ts_min: int, ts_max: int, size_ms: int) -> int:
+    """Windows between the first and the last timestamp's, both included (window number = ts / size truncated,
+    i.e. start = ts - ts % size with the Java remainder)."""
+    def q(t):
+        t = int(t)
+        return t // size_ms if t >= 0 else -((-t) // size_ms)
+    return q(ts_max) - q(ts_min) + 1
+
+
+def plan_slice(mode, kind: str, op: int, val_dtype: int, has_ts: bool, records: int, windows: int,
+               crossover: int = None) -> SlicePlan:
+    """Route one slice().reduceOnEdges / foldNeighbors.  Pure: no GPU, no engine.
+
+    mode: env.getSliceBatching() ("auto", True or False); kind: "reduce", "fold", "degree_max" (the built-ins) or
+    "user"; op / val_dtype: the GS_OP_* / GS_* of a reduce or fold; records: direction-expanded records of the
+    stream; windows: window_span of its timestamps.  The key-width limit of the batched call is not known here:
+    a call it refuses (GS_EUNSUPPORTED) falls back to the loop at run time."""
+    if crossover is None:
+        crossover = SLICE_CROSSOVER
+    if mode is False:
+        return SlicePlan(False, "batching is off", windows)
+    if kind not in ("reduce", "fold", "degree_max"):
+        return SlicePlan(False, "user function: grouped per window", windows)
+    if not has_ts:
+        return SlicePlan(False, "no timestamp column: one window", windows)
+    if windows <= 1:
+        return SlicePlan(False, "a single window", windows)
+    if records > SLICE_MAX_RECORDS:
+        return SlicePlan(False, "more records than one batched call takes", windows)
+    if mode is True:
+        return SlicePlan(True, "batching is on", windows)
+    float_sum = kind != "degree_max" and op == L.GS_OP_SUM and val_dtype in (L.GS_F32, L.GS_F64)
+    if float_sum:
+        return SlicePlan(False, "float SUM is not bit-stable across paths", windows)
+    if records >= crossover * windows:   # mean records per window >= the crossover
+        return SlicePlan(False, "windows at or above the measured crossover", windows)
+    return SlicePlan(True, "windows below the measured crossover", windows)
+
+
 class StreamExecutionEnvironment:
     """Holds the engine (one gs_ctx) — the role of the Flink environment for this path."""
     _default = None
@@ -84,6 +140,22 @@ class StreamExecutionEnvironment:
         self._engine = None
         self._parallelism = 1
         self._micro_batch = None
+        self._slice_batching = "auto"
+        self.last_slice_plan = None                                   # the last slice() operator's SlicePlan
+        self.slice_counts = {"batched": 0, "loop": 0, "refused": 0}   # operators per route; refused: batched -> loop
+
+    def setSliceBatching(self, mode="auto") -> "StreamExecutionEnvironment":
+        """How slice(size).reduceOnEdges / foldNeighbors with a built-in function run a stream of many windows:
+        True = all windows in one engine call (gs_slice_reduce) whenever the stream allows it, False = one call
+        per window, "auto" (default) = batched where that was measured faster and the result is the loop's bit for
+        bit (integers, COUNT, float MIN / MAX, the degree fold; float SUM only under True)."""
+        if mode not in ("auto", True, False) or (mode != "auto" and not isinstance(mode, bool)):
+            raise ValueError('slice batching is "auto", True or False')
+        self._slice_batching = mode
+        return self
+
+    def getSliceBatching(self):
+        return self._slice_batching
 
     def setParallelism(self, parallelism: int) -> "StreamExecutionEnvironment":
         """env.setParallelism: the operators' parallelism; on this path it changes what the windowed
@@ -349,7 +421,7 @@ class SimpleEdgeStream:
         e = self.edges
         if e.ts is None:
             return [(0, size_ms, e, np.arange(len(e)))] if with_index else [(0, size_ms, e)]
-        ts = np.asarray(e.ts, dtype=np.int64)
+        ts = np.asarray(_to_np(e.ts), dtype=np.int64)
         start = ts - np.fmod(ts, size_ms)
         order = np.argsort(start, kind="stable")
         starts, first = np.unique(start[order], return_index=True)
@@ -382,8 +454,51 @@ class GraphWindowStream:
     def _each(self):
         return self.stream._windows(self.size_ms)
 
+    # -- routing: the per-window loop below, or every window in one call ------------------------------------
+    def _plan(self, kind: str, op: int) -> SlicePlan:
+        e, env = self.stream.edges, self.stream.context
+        n = len(e)
+        windows = 1
+        if e.ts is not None and n:
+            windows = window_span(e.ts.min().item() if _is_torch(e.ts) else np.min(e.ts),
+                                  e.ts.max().item() if _is_torch(e.ts) else np.max(e.ts), self.size_ms)
+        dtype = L.GS_NONE if kind == "degree_max" or op == L.GS_OP_COUNT else _gs_dtype(e.val)
+        plan = plan_slice(env.getSliceBatching(), kind, op, dtype, e.ts is not None and n > 0,
+                          Engine._records(n, self.direction), windows)
+        env.last_slice_plan = plan
+        return plan
+
+    def _batched(self, plan: SlicePlan, call) -> DataStream:
+        """call(windows_hint) -> (window_start, row_begin, *row columns); None when the engine refuses the key."""
+        env = self.stream.context
+        try:
+            ws, rb, *cols = call(plan.windows)
+        except GsError as err:
+            if err.status != L.GS_EUNSUPPORTED:
+                raise
+            env.slice_counts["refused"] += 1
+            return None
+        env.slice_counts["batched"] += 1
+        ws, rb = _to_np(ws), _to_np(rb)
+        out = DataStream()
+        for w in range(len(ws)):
+            lo, hi = int(rb[w]), int(rb[w + 1])
+            out.windows.append(WindowOutput(int(ws[w]), int(ws[w]) + self.size_ms, tuple(c[lo:hi] for c in cols)))
+        return out
+
     def reduceOnEdges(self, reduceFunction: EdgesReduce) -> DataStream:
         """:101-104 -> Tuple2<K, EV>(vertex, reduced value) per vertex and window."""
+        builtin = isinstance(reduceFunction, _BuiltinReduce)
+        plan = self._plan("reduce" if builtin else "user", reduceFunction.op if builtin else -1)
+        if plan.batched:
+            e = self.stream.edges
+            if reduceFunction.op != L.GS_OP_COUNT and e.val is None:
+                raise ValueError("reduceOnEdges needs edge values")
+            out = self._batched(plan, lambda hint: self.engine.slice_reduce(
+                e.src, e.dst, e.val, e.ts, self.size_ms, self.direction, reduceFunction.op, windows_hint=hint))
+            if out is not None:
+                return out
+        self.stream.context.slice_counts["loop"] += 1
         out = DataStream()
         for s, t, w in self._each():
             if len(w) == 0:
@@ -405,6 +520,31 @@ class GraphWindowStream:
 
     def foldNeighbors(self, initialValue, foldFunction: EdgesFold) -> DataStream:
         """:62-64 -> one accumulator per vertex and window, folded from a copy of initialValue."""
+        degmax = isinstance(foldFunction, DegreeMaxNeighborFold)
+        builtin = isinstance(foldFunction, _BuiltinFold)
+        plan = self._plan("degree_max" if degmax else "fold" if builtin else "user", foldFunction.op if builtin else -1)
+        if plan.batched:
+            e = self.stream.edges
+            if degmax:
+                init_max = int(initialValue[2]) if len(initialValue) > 2 else -(1 << 63)
+
+                def call(hint):
+                    ws, rb, k, d, m = self.engine.slice_fold_degree_max(e.src, e.dst, e.ts, self.size_ms, self.direction,
+                                                                        init_max, windows_hint=hint)
+                    if int(initialValue[1]) != 0:
+                        d = d + int(initialValue[1])
+                    return ws, rb, k, d, m
+            else:
+                if foldFunction.op != L.GS_OP_COUNT and e.val is None:
+                    raise ValueError("foldNeighbors needs edge values")
+
+                def call(hint):
+                    return self.engine.slice_reduce(e.src, e.dst, e.val, e.ts, self.size_ms, self.direction,
+                                                    foldFunction.op, initialValue[1], windows_hint=hint)
+            out = self._batched(plan, call)
+            if out is not None:
+                return out
+        self.stream.context.slice_counts["loop"] += 1
         out = DataStream()
         for s, t, w in self._each():
             if len(w) == 0:

@@ -214,6 +214,49 @@ GS_API gs_status gs_window_fold_degree_max(gs_ctx* ctx, const gs_edge_batch* bat
  * set a small max_records to force chunking; 0 restores the default. */
 GS_API gs_status gs_set_max_window_records(gs_ctx* ctx, uint64_t max_records);
 
+/* ---- all tumbling windows of a batch in one call -------------------------------------
+ * SimpleEdgeStream.slice(size).reduceOnEdges / foldNeighbors over a batch that spans many windows
+ * (SimpleEdgeStream.java:159-167 keys (vertex, window) state for all open windows at once): the records are
+ * sorted once by (window, vertex) and reduced once.  The rows are the per-window entry points' outputs
+ * concatenated in window order: integers, MIN / MAX and COUNT bit for bit, float sums within the API's 1e-5
+ * relative tolerance (each (window, vertex) group keeps its arrival order).
+ *
+ * ts[i] is edge i's event time, in any order; its window starts at ts - ts % window_ms with the truncated
+ * (Java) remainder, as gs_stream_* assigns it: negative timestamps round toward zero, every ts in
+ * (-window_ms, window_ms) shares window 0.  batch->window_end_ms is ignored.  With GS_DIR_ALL both records of
+ * an edge carry its timestamp.
+ *
+ * Windows come out ascending by start, empty windows not at all; vertices ascend inside a window;
+ * row_begin[*n_windows] == *n_rows.
+ *
+ * The sort key is ((start - min start) / window_ms) << vbits | (vertex - min vertex), vbits the width of the
+ * vertex span over the key column(s) of `dir`, wbits that of the window span.  wbits + vbits > 64:
+ * GS_EUNSUPPORTED (the message names both widths), nothing is written, and the caller falls back to one call
+ * per window.  Every int64 is a legal vertex and a legal timestamp.
+ *
+ * R = n (2n for GS_DIR_ALL) >= 2^32: GS_EINVAL (split the batch at a window boundary).  window_ms <= 0:
+ * GS_EINVAL.  n == 0: zero windows.  A short capacity_windows or capacity_rows: GS_ECAPACITY with both
+ * *n_windows and *n_rows set to what is needed.  Outputs are complete on return for host memory and in the ctx
+ * stream's order for device memory; GS_FLAG_ASYNC_OUTPUT does not apply. */
+typedef struct gs_sliced_out {
+  int64_t*  window_start;     /* [capacity_windows]     starts of the non-empty windows, ascending   */
+  uint64_t* row_begin;        /* [capacity_windows + 1] window w owns rows [row_begin[w], row_begin[w+1]) */
+  int64_t*  keys;             /* [capacity_rows] vertices, ascending inside a window                  */
+  void*     vals;             /* [capacity_rows] batch dtype; I64 for COUNT and for the degree fold   */
+  int64_t*  vals2;            /* degree fold: max neighbour; NULL otherwise                           */
+  uint64_t  capacity_windows, capacity_rows;
+  uint64_t* n_windows;        /* host */
+  uint64_t* n_rows;           /* host */
+  int32_t   mem, reserved;
+} gs_sliced_out;
+
+/* init NULL: reduceOnEdges; else foldNeighbors' init (one host value of the batch dtype, I64 for COUNT) */
+GS_API gs_status gs_slice_reduce(gs_ctx* ctx, const gs_edge_batch* batch, const int64_t* ts, int32_t ts_mem,
+                                 int64_t window_ms, int32_t dir, int32_t op, const void* init, gs_sliced_out* out);
+/* the degree / max-neighbour fold (gs_window_fold_degree_max) per window: vals = degree, vals2 = maximum */
+GS_API gs_status gs_slice_fold_degree_max(gs_ctx* ctx, const gs_edge_batch* batch, const int64_t* ts, int32_t ts_mem,
+                                          int64_t window_ms, int32_t dir, int64_t init_max, gs_sliced_out* out);
+
 /* The grouping half of applyOnNeighbors (GraphWindowStream.java:130-175): the window's
  * neighbourhoods as a CSR in arrival order, for a host-side user EdgesApply to iterate. */
 GS_API gs_status gs_window_csr(gs_ctx* ctx, const gs_edge_batch* batch, int32_t dir, gs_csr_out* out);
