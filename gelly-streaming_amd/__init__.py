@@ -11,10 +11,12 @@ The directory name contains a hyphen, so it is loaded by path:
 or with ``load_package()`` from __graft_entry__.py.
 """
 from ._lib import GsError, load as load_library  # noqa: F401
-from .engine import (AssignComponentsState, CommGroup, ContinuousState, DistinctState, Engine, StageTimes,  # noqa: F401
+from .engine import (AggregateState, AssignComponentsState, CommGroup, ContinuousState, DistinctState, Engine, StageTimes,  # noqa: F401
                      TriangleSamplerState, WeightedMatchingState)
 from .functions import (Collector, CountFold, CountReduce, DegreeMaxNeighborFold, EdgesApply, EdgesFold,  # noqa: F401
-                        EdgesReduce, MaxReduce, MaxValuesFold, MinReduce, MinValuesFold, SumReduce, SumValuesFold)
+                        EdgesReduce, MaxReduce, MaxValuesFold, MinReduce, MinValuesFold, SumReduce, SumValuesFold,
+                        EdgeValueSeparator, GlobalRunningCount, GlobalRunningMax, GlobalRunningMin, GlobalRunningSum,
+                        RunningCount, RunningMax, RunningMin, RunningSum)
 from .stream import (AscendingTimestampExtractor, DataStream, EdgeColumns, EdgeDirection,  # noqa: F401
                      EdgeValueTimestampExtractor, GraphWindowStream, SimpleEdgeStream, SlicePlan,
                      StreamExecutionEnvironment, Time, TimeUnit, plan_slice, window_span)

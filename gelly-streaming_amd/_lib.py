@@ -26,6 +26,7 @@ GS_READBACK_STREAM, GS_READBACK_EARLY, GS_READBACK_EARLY_TIMEOUT = 0, 1, 2   # g
 GS_I32, GS_I64, GS_F32, GS_F64, GS_NONE = 0, 1, 2, 3, 4
 GS_OP_SUM, GS_OP_MIN, GS_OP_MAX, GS_OP_COUNT = 0, 1, 2, 3
 GS_DISTINCT_KEYED, GS_DISTINCT_INSTANCE = 0, 1   # gs_distinct_mode
+GS_AGG_KEYED, GS_AGG_GLOBAL = 0, 1   # gs_agg_mode
 GS_TRISAMPLE_BROADCAST, GS_TRISAMPLE_INCIDENCE = 0, 1   # gs_trisample_mode
 GS_MATCH_ADD, GS_MATCH_REMOVE = 0, 1   # gs_match_event: MatchingEvent.Type ordinals
 GS_TRISAMPLE_TILE = 2048        # edges per tile of the streaming pass
@@ -55,6 +56,8 @@ EXPORTS = ("gs_abi_version", "gs_device_count", "gs_create", "gs_destroy", "gs_l
            "gs_set_max_window_records", "gs_candidates_begin", "gs_candidates_begin_part", "gs_candidates_next", "gs_candidates_next_u32", "gs_candidates_seek",
            "gs_candidates_vertex_range", "gs_cont_create", "gs_cont_destroy", "gs_cont_size", "gs_cont_capacity",
            "gs_cont_degrees", "gs_cont_vertices", "gs_cont_export", "gs_cont_import",
+           "gs_agg_create", "gs_agg_destroy", "gs_agg_size", "gs_agg_capacity", "gs_agg_edges", "gs_agg_global",
+           "gs_agg_export", "gs_agg_import",
            "gs_distinct_create", "gs_distinct_destroy", "gs_distinct_edges", "gs_distinct_size", "gs_distinct_capacity",
            "gs_distinct_export", "gs_distinct_import",
            "gs_trisample_create", "gs_trisample_destroy", "gs_trisample_edges", "gs_trisample_size",
@@ -302,6 +305,14 @@ def load() -> ctypes.CDLL:
         "gs_cont_vertices": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsVertexOut)]),
         "gs_cont_export": (st, [P, P, ctypes.POINTER(GsVertexOut)]),
         "gs_cont_import": (st, [P, P, ctypes.POINTER(GsPartialBatch)]),
+        "gs_agg_create": (st, [P, i32, i32, i32, u64, ctypes.POINTER(P)]),
+        "gs_agg_destroy": (None, [P]),
+        "gs_agg_size": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_agg_capacity": (st, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "gs_agg_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), i32, ctypes.POINTER(GsVertexOut)]),
+        "gs_agg_global": (st, [P, P, ctypes.POINTER(GsEdgeBatch), i32, i32, ctypes.POINTER(GsVertexOut)]),
+        "gs_agg_export": (st, [P, P, ctypes.POINTER(GsVertexOut)]),
+        "gs_agg_import": (st, [P, P, ctypes.POINTER(GsPartialBatch), u64]),
         "gs_distinct_create": (st, [P, i32, u64, ctypes.POINTER(P)]),
         "gs_distinct_destroy": (None, [P]),
         "gs_distinct_edges": (st, [P, P, ctypes.POINTER(GsEdgeBatch), ctypes.POINTER(GsEdgeOut)]),

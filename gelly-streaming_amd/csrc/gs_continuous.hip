@@ -26,23 +26,13 @@
 // could exceed it).  An empty slot holds TAB_EMPTY (the bits of vertex -1); vertex -1 itself lives in a side
 // slot (meta[CT_SIDE], present iff its count != 0).
 // Keys are claimed through gs_table.hpp's tab_claim; counts are touched by their key's one lane.
-#include "gs_table.hpp"
+// The table, its growth and the batch's runs are gs_ctable.hpp's, shared with gs_aggregate.hip.
+#include "gs_ctable.hpp"
 
 namespace gs {
 
-enum { CT_DISTINCT = 0, CT_SIDE = 1, CT_ERR = 2, CT_SUM = 3, CT_META = 4 };   // u64 words of gs_cont::meta
+constexpr int CT_META = 4;   // u64 words of gs_cont::meta (gs_ctable.hpp names them)
 constexpr int CT_EMIT_TILE = 2048;
-
-struct CtTable {
-  unsigned long long* slots;   // [cap][2]: id (or TAB_EMPTY), count -- one 16-byte slot, one line per hit
-  unsigned long long mask;     // cap - 1
-  unsigned long long* meta;
-};
-
-// the slot of `id` (!= TAB_EMPTY: vertex -1 has the side slot), claimed if absent (*fresh); ~0: the table is full
-__device__ __forceinline__ unsigned long long ct_slot(const CtTable& t, unsigned long long id, bool* fresh) {
-  return tab_claim<2>(t.slots, t.mask, id, fresh);
-}
 
 // lane per run u of the batch: base[u] = the vertex's count before the batch, count += the run's length.
 // FLAG_NEW: flags[rec[head]] = 1 for a vertex never seen before (its earliest arrival in the batch).
@@ -79,16 +69,6 @@ __global__ __launch_bounds__(256) void k_ct_upsert(CtTable t, const int64_t* __r
   block_add(&t.meta[CT_DISTINCT], n_fresh, s_part);
 }
 
-// largest u in [lo, hi] with offs[u] <= p (offs[lo] <= p given)
-__device__ __forceinline__ uint32_t ct_run_of(const uint64_t* __restrict__ offs, uint32_t lo, uint32_t hi, uint64_t p) {
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (offs[mid] <= p) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // block per tile of sorted positions: the tile's first and last run by a search over all offsets, then each
 // position's run by a search between the two (a hub's run spans many tiles: the search is then empty)
 __global__ __launch_bounds__(256) void k_ct_emit(const uint64_t* __restrict__ offs, const uint64_t* __restrict__ base,
@@ -107,13 +87,6 @@ __global__ __launch_bounds__(256) void k_ct_emit(const uint64_t* __restrict__ of
   }
 }
 
-// the vertex column of the degree records needs no sort: record 2i is src[i], 2i + 1 is dst[i] (ALL)
-__global__ __launch_bounds__(256) void k_ct_expand_all(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
-                                                       uint64_t n, int64_t* __restrict__ out_v) {
-  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < 2 * n; r += (uint64_t)gridDim.x * 256)
-    out_v[r] = (r & 1) ? dst[r >> 1] : src[r >> 1];
-}
-
 // arrival position r flagged as a first occurrence -> output row pos[r]: (vertex, running numberOfVertices)
 __global__ __launch_bounds__(256) void k_ct_compact(const uint64_t* __restrict__ flags, const uint64_t* __restrict__ pos,
                                                     uint32_t R, const int64_t* __restrict__ src,
@@ -124,26 +97,6 @@ __global__ __launch_bounds__(256) void k_ct_compact(const uint64_t* __restrict__
     const uint64_t k = pos[r];
     out_v[k] = (r & 1) ? dst[r >> 1] : src[r >> 1];   // ALL: record 2i = src[i], 2i + 1 = dst[i]
     out_c[k] = (int64_t)(distinct_before + k + 1);
-  }
-}
-
-// every slot free: (TAB_EMPTY, 0)
-__global__ __launch_bounds__(256) void k_ct_clear(ulonglong2* __restrict__ slots, uint64_t cap) {
-  for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * 256)
-    slots[s] = make_ulonglong2(TAB_EMPTY, 0ull);
-}
-
-// growth: every entry of the old table into the new one (keys distinct: claims only)
-__global__ __launch_bounds__(256) void k_ct_rehash(const ulonglong2* __restrict__ oslots, uint64_t ocap,
-                                                   CtTable t) {
-  for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < ocap; s += (uint64_t)gridDim.x * 256) {
-    const ulonglong2 o = oslots[s];
-    const unsigned long long id = o.x;
-    if (id == TAB_EMPTY) continue;
-    bool fresh;
-    const unsigned long long d = ct_slot(t, id, &fresh);
-    if (d == ~0ull) atomicOr(&t.meta[CT_ERR], 1ull);
-    else t.slots[2 * d + 1] = o.y;
   }
 }
 
@@ -221,53 +174,6 @@ namespace {
 
 CtTable table_of(const gs_cont* t) { return CtTable{t->slots, t->cap - 1, t->meta}; }
 
-// a table of cap free slots (cleared in the ctx stream's order)
-gs_status alloc_table(gs_ctx* c, uint64_t cap, unsigned long long** slots) {
-  *slots = nullptr;
-  if (cap > (1ull << 40) || hipMalloc((void**)slots, cap * 16) != hipSuccess) {
-    (void)hipGetLastError();
-    *slots = nullptr;
-    return set_error(c, GS_ENOMEM, "continuous state: a vertex table of %llu slots does not fit",
-                     (unsigned long long)cap);
-  }
-  hipLaunchKernelGGL(k_ct_clear, dim3(tab_grid(cap)), dim3(256), 0, c->stream, (ulonglong2*)*slots, cap);
-  const gs_status st = hip_check(c, hipGetLastError(), "k_ct_clear");
-  if (st != GS_OK) {
-    hipFree(*slots);
-    *slots = nullptr;
-  }
-  return st;
-}
-
-// room for `need` distinct vertices at load <= 1/2: grow by doubling (allocate, re-insert, swap).  On any
-// failure the old table stays as it was.
-gs_status reserve(gs_ctx* c, gs_cont* t, uint64_t need) {
-  if (need <= t->cap / 2) return GS_OK;
-  uint64_t cap, doublings;
-  // a table of 2^40 slots may still double: alloc_table refuses the 2^41 it plans
-  if (!tab_plan_growth(t->cap, need, 1ull << 41, &cap, &doublings))
-    return set_error(c, GS_ENOMEM, "continuous state: %llu vertices", (unsigned long long)need);
-  unsigned long long* ns;
-  GS_TRY(alloc_table(c, cap, &ns));
-  gs_status st = GS_OK;
-  if (t->distinct) {
-    hipLaunchKernelGGL(k_ct_rehash, dim3(tab_grid(t->cap)), dim3(256), 0, c->stream, (const ulonglong2*)t->slots, t->cap,
-                       CtTable{ns, cap - 1, t->meta});
-    st = hip_check(c, hipGetLastError(), "k_ct_rehash");
-  }
-  if (st == GS_OK) st = tab_read_meta(c, t->meta, CT_META);
-  if (st == GS_OK && c->host_small[8 + CT_ERR]) st = set_error(c, GS_EDEVICE, "continuous state: re-insert failed");
-  if (st != GS_OK) {
-    hipFree(ns);
-    return st;
-  }
-  hipFree(t->slots);
-  t->slots = ns;
-  t->cap = cap;
-  t->growths += doublings;
-  return GS_OK;
-}
-
 gs_status check_state(gs_ctx* c, const gs_cont* t) {
   if (!c) return GS_EINVAL;
   if (!t) return set_error(c, GS_EINVAL, "null continuous state");
@@ -308,18 +214,13 @@ gs_status cont_batch(gs_ctx* c, gs_cont* t, const gs_edge_batch* b, int32_t dir,
   const void* val;
   GS_TRY(stage_batch(c, b, &src, &dst, &val, false));
   Sorted s;
-  GS_TRY(sort_window(c, src, dst, nullptr, 0, b->n, dir, PAY_IDX, &s));
   int64_t* rk = c->ct[0].as<int64_t>();
   uint64_t* offs = c->ct[1].as<uint64_t>();
   uint64_t* base = c->ct[2].as<uint64_t>();
-  GS_HIP(hipMemsetAsync(offs, 0, 8, c->stream));
   uint64_t U = 0;
-  GS_TRY((s.wide ? launch_rbk<uint64_t, CountOp>(c, s, CsrOut{rk, offs}, &U)
-                 : launch_rbk<uint32_t, CountOp>(c, s, CsrOut{rk, offs}, &U)));
-  if (U == 0 || U > R) return set_error(c, GS_EDEVICE, "continuous state: %llu runs in %llu records",
-                                        (unsigned long long)U, (unsigned long long)R);
+  GS_TRY(ct_sorted_runs(c, src, dst, b->n, dir, R, &s, rk, offs, &U));
   // the batch brings at most U new vertices: room for them at load <= 1/2, or the call ends here
-  GS_TRY(reserve(c, t, t->distinct + U));
+  GS_TRY(ct_reserve(c, t, t->distinct + U, CT_META));
   const uint32_t* rec = (const uint32_t*)s.vals;
   const uint64_t before = t->distinct;
   // ---- the table changes from here on ----
@@ -379,7 +280,7 @@ gs_status gs_cont_create(gs_ctx* c, uint64_t reserve_vertices, gs_cont** out) {
   t->device = c->device;
   t->cap = 64;
   while (t->cap / 2 < reserve_vertices) t->cap *= 2;
-  gs_status st = alloc_table(c, t->cap, &t->slots);
+  gs_status st = ct_alloc_table(c, t->cap, &t->slots);
   if (st == GS_OK && hipMalloc((void**)&t->meta, CT_META * 8) != hipSuccess) {
     (void)hipGetLastError();
     st = set_error(c, GS_ENOMEM, "gs_cont_create: state words");
@@ -493,7 +394,7 @@ gs_status gs_cont_import(gs_ctx* c, gs_cont* t, const gs_partial_batch* rows) {
     GS_HIP(hipMemsetAsync(t->meta + CT_ERR, 0, 8, c->stream));
     return set_error(c, GS_EINVAL, "gs_cont_import: every count must be at least 1");
   }
-  GS_TRY(reserve(c, t, n));
+  GS_TRY(ct_reserve(c, t, n, CT_META));
   // ---- the table changes from here on ----
   hipLaunchKernelGGL(k_ct_import, dim3(tab_grid_tab(n)), dim3(256), 0, c->stream, table_of(t), dk, dc, n);
   GS_HIP(hipGetLastError());

@@ -113,6 +113,8 @@ struct gs_ctx {
   gs::DevBuf ct[5];              // continuous streams (gs_continuous.hip): run keys, offsets, bases, flags, scan;
                                  // gs_distinct.hip: [0] held slots, [3] keep flags, [4] their scan
                                  // gs_assign.hip: [0] edge keys of the second sort, [1] / [2] record numbers
+                                 // gs_aggregate.hip: run keys, offsets, bases, slots (global: update flags, the one
+                                 // run, all values, their scan), [4] sorted values + tile aggregates
   gs::DevBuf ts[12];             // sampling triangle estimators (gs_trisample.hip): epochs, wanted table, events;
                                  // gs_matching.hip: per-edge slots, pending lists, footprints, event scratch
                                  // gs_assign.hip: per-edge slots, roots, live lists, losers; record scratch; [11] growth map

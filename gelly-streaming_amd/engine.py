@@ -742,6 +742,12 @@ class Engine:
         (getDegrees / getInDegrees / getOutDegrees / getVertices / numberOfVertices): one per operator."""
         return ContinuousState(self, reserve_vertices)
 
+    def aggregate_state(self, op, dtype, mode: str = "keyed", reserve_vertices: int = 0) -> "AggregateState":
+        """gs_agg_create: an empty device-resident state for SimpleEdgeStream.aggregate (mode "keyed": a running
+        SUM / MIN / MAX / COUNT of the edge values per vertex) or globalAggregate (mode "global": one running
+        value for the stream).  op: L.GS_OP_*; dtype: L.GS_I32 / I64 / F32 / F64 (L.GS_NONE or None: COUNT only)."""
+        return AggregateState(self, op, dtype, mode, reserve_vertices)
+
     def distinct(self, mode: str = "keyed", reserve_edges: int = 0) -> "DistinctState":
         """gs_distinct_create: an empty device-resident edge set for SimpleEdgeStream.distinct().  mode "keyed":
         an edge passes iff its (src, dst) pair is new; "instance": iff its dst is new (the literal
@@ -1063,6 +1069,88 @@ class ContinuousState(_DeviceState):
             counts = np.ascontiguousarray(counts, dtype=np.int64)
         pb, keep, dev = self.engine._partial_batch(keys, counts)
         self.engine._check(self._L.gs_cont_import(self.engine.ctx, self.handle, ctypes.byref(pb)))
+
+
+class AggregateState(_DeviceState):
+    """gs_agg: the state of one SimpleEdgeStream.aggregate / globalAggregate with built-in mappers
+    (include/gelly_hip.h, "aggregate / globalAggregate") -- vertex -> running accumulator in HBM across calls
+    (keyed), or the stream's one accumulator (global).  Feed it the stream in batches of any size: the
+    concatenated outputs depend only on the stream.  Columns are numpy arrays (results come back as numpy) or
+    CUDA tensors of the engine's device (results stay in HBM)."""
+
+    _DESTROY, _SIZE, _CAPACITY = "gs_agg_destroy", "gs_agg_size", "gs_agg_capacity"
+    MODES = {"keyed": L.GS_AGG_KEYED, "global": L.GS_AGG_GLOBAL}
+
+    def __init__(self, engine: Engine, op, dtype, mode: str = "keyed", reserve_vertices: int = 0):
+        if mode not in self.MODES:
+            raise ValueError(f"mode {mode!r}: 'keyed' or 'global'")
+        self.op, self.mode = int(op), mode
+        self.dtype = L.GS_NONE if dtype is None else int(dtype)
+        super().__init__(engine, "gs_agg_create", self.MODES[mode], self.op, self.dtype, int(reserve_vertices))
+        # the accumulator: the value dtype, int64 for COUNT
+        self.acc_dtype = np.int64 if self.op == L.GS_OP_COUNT else L.NP_DTYPE[self.dtype]
+
+    def _run(self, call, b, dev, R, out):
+        e = self.engine
+        if out is not None:
+            e._check_out(out, dev, (np.int64, self.acc_dtype), R)
+            keys, vals = out
+        else:
+            keys, vals = e._empty(dev, R, np.int64), e._empty(dev, R, self.acc_dtype)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(_ptr(keys), _ptr(vals), R, ctypes.pointer(n_out), L.GS_MEM_DEVICE if dev else L.GS_MEM_HOST, 0)
+        e._check(call(ctypes.byref(b), ctypes.byref(vo)))
+        n = n_out.value
+        return keys[:n], vals[:n]
+
+    def edges(self, src, dst, val, direction, out=None):
+        """gs_agg_edges (keyed): one (vertex, accumulator so far) per record of the batch, in arrival order --
+        edge i gives (src[i], .) under OUT, (dst[i], .) under IN, both in that order under ALL.  val: the edge
+        values in the state's dtype (None for a COUNT state created without one).  out: optional (vertices,
+        accumulators) device tensors of at least the batch's records, reused across batches."""
+        b, keep, dev = self.engine._batch(src, dst, val)
+        R = self.engine._records(b.n, direction)
+        call = lambda pb, po: self._L.gs_agg_edges(self.engine.ctx, self.handle, pb, int(direction), po)
+        return self._run(call, b, dev, R, out)
+
+    def global_(self, src, dst, val, direction, collect_updates, out=None):
+        """gs_agg_global (global): per record the running value of the whole stream and the record's vertex;
+        with collect_updates only the records at which the value changes (Java equals on the boxed value)."""
+        b, keep, dev = self.engine._batch(src, dst, val)
+        R = self.engine._records(b.n, direction)
+        call = lambda pb, po: self._L.gs_agg_global(self.engine.ctx, self.handle, pb, int(direction),
+                                                    1 if collect_updates else 0, po)
+        return self._run(call, b, dev, R, out)
+
+    def size(self):
+        """gs_agg_size: (distinct vertices, records) seen so far (global: 1 vertex once a record was seen)."""
+        return self._pair(self._SIZE)
+
+    def capacity(self):
+        """gs_agg_capacity: (slots of the table, doublings so far); a global state has no table: (0, 0)."""
+        return self._pair(self._CAPACITY)
+
+    def export(self, device: bool = False):
+        """gs_agg_export: the checkpoint (vertices ascending, accumulators), numpy or (device=True) CUDA tensors;
+        a global state gives no row or the one row (0, accumulator)."""
+        e = self.engine
+        D = self.size()[0]
+        keys, vals = e._empty(device, D, np.int64), e._empty(device, D, self.acc_dtype)
+        n_out = ctypes.c_uint64(0)
+        vo = L.GsVertexOut(_ptr(keys), _ptr(vals), D, ctypes.pointer(n_out), L.GS_MEM_DEVICE if device else L.GS_MEM_HOST, 0)
+        e._check(self._L.gs_agg_export(e.ctx, self.handle, ctypes.byref(vo)))
+        n = n_out.value
+        return keys[:n], vals[:n]
+
+    def load(self, keys, vals, records):
+        """gs_agg_import: restore a checkpoint (vertices, accumulators, the records it had seen) into this, still
+        empty, state."""
+        if _is_torch(keys):
+            vals = vals.to(_out_dtypes()[self.acc_dtype])
+        else:
+            vals = np.ascontiguousarray(vals, dtype=self.acc_dtype)
+        pb, keep, dev = self.engine._partial_batch(keys, vals)
+        self.engine._check(self._L.gs_agg_import(self.engine.ctx, self.handle, ctypes.byref(pb), int(records)))
 
 
 class DistinctState(_DeviceState):

@@ -24,8 +24,8 @@ import numpy as np
 
 from . import _lib as L
 from .engine import Engine, GsError, _gs_dtype, _is_torch
-from .functions import (Collector, EdgesApply, EdgesFold, EdgesReduce, DegreeMaxNeighborFold, _BuiltinFold,
-                        _BuiltinReduce)
+from .functions import (Collector, EdgesApply, EdgesFold, EdgesReduce, DegreeMaxNeighborFold, EdgeValueSeparator,
+                        _BuiltinFold, _BuiltinGlobalRunning, _BuiltinReduce, _BuiltinRunning, java_equals)
 
 
 class EdgeDirection(IntEnum):
@@ -316,9 +316,74 @@ class SimpleEdgeStream:
         ts = None if e.ts is None else np.repeat(np.asarray(e.ts), 2)
         return SimpleEdgeStream(EdgeColumns(src, dst, val, ts), self.context)
 
-    def aggregate(self, graphAggregation) -> "DataStream":
-        """GraphStream.aggregate (SimpleEdgeStream.java:104-106): e.g. ConnectedComponents(mergeWindowTime)."""
-        return graphAggregation.run(self)
+    def aggregate(self, graphAggregation, vertexMapper=None) -> "DataStream":
+        """One argument: GraphStream.aggregate (SimpleEdgeStream.java:104-106), e.g.
+        ConnectedComponents(mergeWindowTime).
+
+        Two arguments, aggregate(edgeMapper, vertexMapper) (:493-498: flatMap -> keyBy(0) -> map): a running value
+        per vertex, one record (vertex, value) per record the edge mapper emits, in arrival order.  An
+        EdgeValueSeparator with RunningSum / RunningMin / RunningMax / RunningCount runs on the device through one
+        fresh state in env.getMicroBatch()-sized batches (the result does not depend on that size); any other
+        pair is user code, called record by record on the host: edgeMapper.flatMap(edge, out) (or
+        edgeMapper(edge, out)) with edge = (source, target, value) and out a Collector, then vertexMapper.map(record)
+        (or vertexMapper(record)) on each collected record."""
+        if vertexMapper is None:
+            return graphAggregation.run(self)
+        edgeMapper = graphAggregation
+        if isinstance(edgeMapper, EdgeValueSeparator) and isinstance(vertexMapper, _BuiltinRunning):
+            return self._device_aggregate(edgeMapper, vertexMapper, "keyed", False)
+        vmap = getattr(vertexMapper, "map", vertexMapper)
+        return DataStream([WindowOutput(0, 0, ("records", [vmap(r) for r in self._host_records(edgeMapper)]))])
+
+    def globalAggregate(self, edgeMapper, vertexMapper, collectUpdates: bool) -> "DataStream":
+        """:509-539 -> the same at parallelism 1 with one value for the whole stream (bare values); with
+        collectUpdates only the values that differ (Java equals) from the one before them.  An EdgeValueSeparator
+        with GlobalRunningSum / Min / Max / Count runs on the device; any other pair on the host:
+        vertexMapper.flatMap(record, out) (or vertexMapper(record, out)) collects the values."""
+        if isinstance(edgeMapper, EdgeValueSeparator) and isinstance(vertexMapper, _BuiltinGlobalRunning):
+            return self._device_aggregate(edgeMapper, vertexMapper, "global", collectUpdates)
+        vflat = getattr(vertexMapper, "flatMap", vertexMapper)
+        out = Collector()
+        for r in self._host_records(edgeMapper):
+            vflat(r, out)
+        values = out.records
+        if collectUpdates:   # GlobalAggregateMapper :525-539
+            kept, prev = [], None
+            for v in values:
+                if not java_equals(v, prev):
+                    prev = v
+                    kept.append(v)
+            values = kept
+        return DataStream([WindowOutput(0, 0, ("records", values))])
+
+    def _host_records(self, edgeMapper):
+        """The records a user edge mapper collects, edge by edge in arrival order."""
+        e = self.edges
+        eflat = getattr(edgeMapper, "flatMap", edgeMapper)
+        src, dst, val = _to_np(e.src), _to_np(e.dst), _to_np(e.val)
+        out = Collector()
+        for i in range(len(src)):
+            eflat((src[i].item(), dst[i].item(), None if val is None else val[i].item()), out)
+        return out.records
+
+    def _device_aggregate(self, edgeMapper, vertexMapper, mode: str, collect_updates: bool) -> "DataStream":
+        e = self.edges
+        n = len(e)
+        count = vertexMapper.op == L.GS_OP_COUNT
+        if e.val is None and not count:
+            raise ValueError("aggregate: the stream has no edge values")
+        mb = self.context.getMicroBatch() or max(n, 1)
+        out = DataStream()
+        with self.context.engine.aggregate_state(vertexMapper.op, _gs_dtype(e.val), mode) as state:
+            for a in range(0, n, mb):
+                src, dst, val = e.src[a:a + mb], e.dst[a:a + mb], None if e.val is None else e.val[a:a + mb]
+                if mode == "keyed":
+                    cols = state.edges(src, dst, val, edgeMapper.direction)
+                else:
+                    vals = state.global_(src, dst, val, edgeMapper.direction, collect_updates)[1]
+                    cols = ("records", [x.item() for x in _to_np(vals)])
+                out.windows.append(WindowOutput(0, 0, cols))
+        return out
 
     # -- the continuous operators: one device state per call, fed in micro-batches (env.setMicroBatch) ----
     # Records come out in the reference's order at parallelism 1 whatever env.getParallelism() says (at

@@ -577,6 +577,59 @@ GS_API gs_status gs_cont_export(gs_ctx* ctx, const gs_cont* state, gs_vertex_out
  * counts >= 1 (GS_EINVAL otherwise), any order; records = the sum of the counts. */
 GS_API gs_status gs_cont_import(gs_ctx* ctx, gs_cont* state, const gs_partial_batch* rows);
 
+/* ---- aggregate / globalAggregate: running values that outlive a window ------------------------- */
+/* SimpleEdgeStream.aggregate(edgeMapper, vertexMapper) (SimpleEdgeStream.java:493-498) is flatMap -> keyBy(0) ->
+ * map: a running value per vertex, one output record per input record.  globalAggregate(edgeMapper, vertexMapper,
+ * collectUpdates) (:509-539) is the same at parallelism 1 with one value for the whole stream, optionally
+ * emitted only when it changes.  A gs_agg runs both with built-in mappers: the edge mapper is
+ * DegreeTypeSeparator's order (:444-463) carrying the edge's value where that class puts 1L -- edge i contributes
+ * (src[i], val[i]) then (dst[i], val[i]) as `dir` collects them, R = n records, 2n under GS_DIR_ALL -- and the
+ * vertex mapper combines with `op`:
+ *   GS_AGG_KEYED   a HashMap<K, VV>: the state is gs_cont's kind of table, vertex -> accumulator, in HBM.
+ *   GS_AGG_GLOBAL  one accumulator for the stream, no table.
+ * op: GS_OP_SUM | MIN | MAX | COUNT; val_dtype: GS_I32 | I64 | F32 | F64 (GS_NONE only with GS_OP_COUNT).  The
+ * accumulator has the value's dtype, I64 for COUNT.  The combine rules are gs_window_reduce's: an integer SUM
+ * wraps at its own width; MIN / MAX follow Math.min / Math.max (NaN wins, -0.0 < +0.0); a vertex's (the
+ * stream's) first value is its accumulator unchanged, so a first -0.0 under SUM stays -0.0.  A float SUM is NaN
+ * or infinite where the arrival-order fold of the same values is.
+ * The concatenated outputs depend only on the stream, never on where it was cut into batches: bit for bit for
+ * integers, COUNT, MIN / MAX and float sums whose partial sums are all exact; a general float SUM is associated
+ * differently from the arrival-order fold (and per cut) and agrees with it within rounding.
+ * Every int64 is a legal vertex, -1 included.  One state serves one operator; use it from one thread at a time,
+ * with a ctx of its device.  A call that returns GS_EINVAL, GS_ECAPACITY or GS_ENOMEM leaves the state exactly
+ * as it was.  A bad dir, a batch whose val_dtype is not the state's, or the other mode's entry point: GS_EINVAL.
+ * Batches hold at most 2^32 - 1 records.  Outputs are complete on return (host memory) or in the order of the
+ * ctx's stream (device memory). */
+typedef enum gs_agg_mode { GS_AGG_KEYED = 0, GS_AGG_GLOBAL = 1 } gs_agg_mode;
+typedef struct gs_agg gs_agg;
+/* An empty state; keyed: with room for reserve_vertices distinct vertices before its first growth. */
+GS_API gs_status gs_agg_create(gs_ctx* ctx, int32_t mode, int32_t op, int32_t val_dtype, uint64_t reserve_vertices,
+                               gs_agg** out);
+GS_API void gs_agg_destroy(gs_agg* state);
+/* Distinct vertices (global: 1 once a record was seen) and records seen so far (either pointer may be NULL). */
+GS_API gs_status gs_agg_size(const gs_agg* state, uint64_t* distinct_vertices, uint64_t* records);
+/* The table's slots (global: 0) and how often it has doubled (either pointer may be NULL). */
+GS_API gs_status gs_agg_capacity(const gs_agg* state, uint64_t* slots, uint64_t* growths);
+/* Keyed: out holds R records (vertex, accumulator) in ARRIVAL order; each accumulator is the combine of every
+ * value of that vertex seen so far in the whole stream, itself included.  GS_OP_COUNT reproduces gs_cont_degrees
+ * record for record.  capacity < R: GS_ECAPACITY with *n_out = R. */
+GS_API gs_status gs_agg_edges(gs_ctx* ctx, gs_agg* state, const gs_edge_batch* batch, int32_t dir, gs_vertex_out* out);
+/* Global: record r carries the combine of all record values of the stream up to and including it.  With
+ * collect_updates != 0 only the records whose value differs from the previous record's (the last record of the
+ * previous batch for the first) are kept, in order; the stream's first record is always kept.  The comparison is
+ * Java equals on Long / Double: the bits, every NaN as one, so 0.0 and -0.0 differ (GlobalAggregateMapper
+ * :525-539).  out->keys may be NULL (else: each kept record's vertex); *n_out = the records kept.
+ * capacity < R: GS_ECAPACITY with *n_out = R, with or without collect_updates. */
+GS_API gs_status gs_agg_global(gs_ctx* ctx, gs_agg* state, const gs_edge_batch* batch, int32_t dir,
+                               int32_t collect_updates, gs_vertex_out* out);
+/* Checkpoint: every (vertex, accumulator), ascending by vertex, vals in the accumulator dtype; a global state
+ * gives 0 rows or the one row (0, accumulator).  capacity < the rows: GS_ECAPACITY with *n_out = that number. */
+GS_API gs_status gs_agg_export(gs_ctx* ctx, const gs_agg* state, gs_vertex_out* out);
+/* Restore a checkpoint into an EMPTY state (GS_EINVAL otherwise): rows->keys = vertices (each once; ignored by a
+ * global state, which takes at most one row), rows->vals = accumulators of the accumulator dtype, any value;
+ * records = the records the checkpointed state had seen (>= rows->n, and 0 for no rows). */
+GS_API gs_status gs_agg_import(gs_ctx* ctx, gs_agg* state, const gs_partial_batch* rows, uint64_t records);
+
 /* ---- distinct(): a device-resident edge set ------------------------------------------------------ */
 /* SimpleEdgeStream.distinct() (SimpleEdgeStream.java:305-327) is edges.keyBy(0).flatMap(DistinctEdgeMapper).
  * The reference's code, Javadoc and test disagree about it, so a gs_distinct offers both readings as modes
